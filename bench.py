@@ -19,7 +19,17 @@ The scene is uploaded before timing (inputs resident in HBM). The timed
 region holds exactly K steps bracketed by barrier + synchronize; the
 reported time is the max over ranks.
 
-Printed JSON line (rank 0): metric/value/unit per BASELINE.json, plus
+A plain run does only what the headline figure needs: it uploads the scene,
+counts one frame's rays (one counted fast-path frame), allocates the render
+streams' workspaces, warms up, times the K steps and prints the JSON line
+(rank 0): metric/value/unit per BASELINE.json, ms_per_step, the configuration
+and the traced-ray counts. `--dump-outputs DIR` also writes the last timed
+frame's canvas (what a caller of the timed path receives) to DIR/canvas.npy.
+
+`--full` adds everything else the benchmark measures and checks, each in runs
+of its own outside the timed region: the bitwise check of the last timed frame
+against the exhaustive (every-shape loop) frame, the per-rank phase split (N
+GPUs), the end-to-end, distinct-camera and cold-start timings, and
   roofline      f64 VALU roofline of the dominant trace-kernel class of the
                 wavefront pipeline; kernel time from HIP events carried by its
                 launches in a serialized pass of the same K frames (one stream,
@@ -125,6 +135,15 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=64)  # whole batches of 8 and 16
     p.add_argument("--warmup", type=int, default=16)
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need (off by default): the bitwise check of the "
+                        "timed frames against the exhaustive frame, the serialized pass for the roofline and the "
+                        "per-class table, the per-rank phase split, end-to-end / distinct-camera / cold-start timings "
+                        "and the CPU baseline (the --no-* options below switch parts of it off)")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write the last timed frame's canvas (rank 0's assembled frame) to "
+                        "DIR/canvas.npy as float64; a canvas above 60 MB is written as a fixed, seeded sample of "
+                        "its pixels")
     p.add_argument("--config", default="c3", choices=["c3", "c5"],
                    help="c3: the headline workload (default); c5: 4096x4096, 4 planes + 9996 spheres, 2 lights, "
                         "depth 8 (SURVEY.md §8d C5; sizes below override)")
@@ -565,20 +584,26 @@ def main():
 
     # exact work counters of one frame (deterministic), from a counted warm-up launch
     # (this first launch also sizes the wavefront queues of this camera/shard)
-    st = render([cam], [shard.data_ptr()], stream.cuda_stream, True, exhaustive=True)
-    assert st["exhaustive"]
-    # the exhaustive frame (the reference's every-shape loop) that the timed fast-path frames must equal
-    ref_shard = shard.clone()
-    counts = torch.tensor([st["rays_primary"], st["rays_reflect"], st["rays_refract"], st["rays_shadow"],
-                           st["sphere_tests"], st["plane_tests"], st["sphere_disc_ge0"]],
+    # --full: the exhaustive frame (the reference's every-shape loop), which the timed
+    # fast-path frames must equal and whose test counters price the reference's work;
+    # a plain run: one counted fast-path frame (the same reference ray counts, and the
+    # traced-ray counters of the result line)
+    st = render([cam], [shard.data_ptr()], stream.cuda_stream, True, exhaustive=a.full)
+    ref_shard, ref_work = None, None
+    if a.full:
+        assert st["exhaustive"]
+        ref_shard = shard.clone()
+    counts = torch.tensor([st["rays_primary"], st["rays_reflect"], st["rays_refract"], st["rays_shadow"]]
+                          + ([st["sphere_tests"], st["plane_tests"], st["sphere_disc_ge0"]] if a.full else [0, 0, 0]),
                           dtype=torch.float64, device=dev)
     if n > 1:
         dist.all_reduce(counts)
     rays_per_frame = float(counts[:4].sum())
-    # SURVEY §8(d) reference work F of one frame (the reference's exhaustive general-4x4
-    # loop): 57 per sphere test, 34 per plane test, +6 per disc >= 0 (exact counters)
-    ref_work = (SURVEY_OPS_SPHERE * float(counts[4]) + SURVEY_OPS_PLANE * float(counts[5])
-                + SURVEY_OPS_ROOTS * float(counts[6]))
+    if a.full:
+        # SURVEY §8(d) reference work F of one frame (the reference's exhaustive general-4x4
+        # loop): 57 per sphere test, 34 per plane test, +6 per disc >= 0 (exact counters)
+        ref_work = (SURVEY_OPS_SPHERE * float(counts[4]) + SURVEY_OPS_PLANE * float(counts[5])
+                    + SURVEY_OPS_ROOTS * float(counts[6]))
     # setup: one batch on each render stream allocates that stream's workspace
     # (queue arenas, counters), so the timed region never meets a first
     # allocation whatever --warmup is (with batches: a whole batch, and the timed
@@ -618,39 +643,43 @@ def main():
     # every asynchronous frame's device-side check (rt_scene_check): a frame left
     # incomplete raises here instead of passing unnoticed
     world.check()
-    # Parity of the timed frames (outside the timed region): the last frame each
-    # rank rendered, and rank 0's assembled canvas, must equal the exhaustive frame
-    # bit for bit (camera.rs:133-148 renders every pixel with the every-shape loop).
-    parity = None if a.no_verify_frames else verify_frames(fa, last, ref_shard, last_frame[0], n, rank, H)
-    # Where an N-rank frame's time goes (outside the timed region, same streams and
-    # batches): the renders alone, and the assembly (gathers + un-interleave) alone
-    split = None
-    if n > 1:
-        split = phase_split(a, n, rank, dev, run_frames, fa, F, NB)
-    # Serialized pass (outside the timed region): the same K frames in the same
-    # batches (the benched launches: NB frames per launch), one batch after the
-    # other on one stream, every launch carrying its own start/stop HIP events
-    # (hipExtLaunchKernel), for the roofline's per-launch kernel time and the
-    # per-class table (per frame: a batch's time / NB). With batches in flight the
-    # timed region overlaps kernels of different batches, so a launch's duration
-    # there includes the CUs it waited for; here each kernel runs alone, as in the
-    # rocprofv3 kernel trace.
-    sbufs = [torch.empty_like(shard) for _ in range(NB)] if NB > 1 else [shard]
-    # (the current stream's workspace has rendered single frames so far: one untimed
-    # batch of NB first, so that an outgrown arena is not met inside the pass)
-    settled(lambda: render([cam] * NB, [b.data_ptr() for b in sbufs[:NB]], stream.cuda_stream))
-    rtamd._rtamd._wf_profile(world, 1, False)
-    for s0 in range(0, a.steps, NB):
-        nf = min(NB, a.steps - s0)
-        render([cam] * nf, [b.data_ptr() for b in sbufs[:nf]], stream.cuda_stream)
-    torch.cuda.synchronize()
-    del sbufs
-    rtamd._rtamd._wf_profile(world, 0, False)
-    # the fast path's own counters (what the kernels executed and traced), one counted
-    # frame on the same workspace: the timed and profiled kernels do not count
-    fst = render([cam], [shard.data_ptr()], stream.cuda_stream, True, exhaustive=False)
-    breakdown = rtamd._rtamd._wf_profile(world, -1, True)  # class times of the profiled frames, counters of the counted one
-    prof = breakdown
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"canvas": last})
+    parity, split, prof, breakdown, fst = None, None, None, None, st
+    if a.full:
+        # Parity of the timed frames (outside the timed region): the last frame each
+        # rank rendered, and rank 0's assembled canvas, must equal the exhaustive frame
+        # bit for bit (camera.rs:133-148 renders every pixel with the every-shape loop).
+        parity = None if a.no_verify_frames else verify_frames(fa, last, ref_shard, last_frame[0], n, rank, H)
+        # Where an N-rank frame's time goes (outside the timed region, same streams and
+        # batches): the renders alone, and the assembly (gathers + un-interleave) alone
+        split = None
+        if n > 1:
+            split = phase_split(a, n, rank, dev, run_frames, fa, F, NB)
+        # Serialized pass (outside the timed region): the same K frames in the same
+        # batches (the benched launches: NB frames per launch), one batch after the
+        # other on one stream, every launch carrying its own start/stop HIP events
+        # (hipExtLaunchKernel), for the roofline's per-launch kernel time and the
+        # per-class table (per frame: a batch's time / NB). With batches in flight the
+        # timed region overlaps kernels of different batches, so a launch's duration
+        # there includes the CUs it waited for; here each kernel runs alone, as in the
+        # rocprofv3 kernel trace.
+        sbufs = [torch.empty_like(shard) for _ in range(NB)] if NB > 1 else [shard]
+        # (the current stream's workspace has rendered single frames so far: one untimed
+        # batch of NB first, so that an outgrown arena is not met inside the pass)
+        settled(lambda: render([cam] * NB, [b.data_ptr() for b in sbufs[:NB]], stream.cuda_stream))
+        rtamd._rtamd._wf_profile(world, 1, False)
+        for s0 in range(0, a.steps, NB):
+            nf = min(NB, a.steps - s0)
+            render([cam] * nf, [b.data_ptr() for b in sbufs[:nf]], stream.cuda_stream)
+        torch.cuda.synchronize()
+        del sbufs
+        rtamd._rtamd._wf_profile(world, 0, False)
+        # the fast path's own counters (what the kernels executed and traced), one counted
+        # frame on the same workspace: the timed and profiled kernels do not count
+        fst = render([cam], [shard.data_ptr()], stream.cuda_stream, True, exhaustive=False)
+        breakdown = rtamd._rtamd._wf_profile(world, -1, True)  # class times of the profiled frames, counters of the counted one
+        prof = breakdown
     if a.verify and rank == 0:  # dev: the assembled last frame equals a one-GPU render of the whole frame
         whole = torch.empty((H, W, 3), dtype=torch.float64, device=dev)
         cam.render_shard_device(world, depth, B, 0, 1, whole.data_ptr(), stream.cuda_stream, False)
@@ -710,23 +739,27 @@ def main():
                 "assembler_fallback": assembler_fallback,
                 "dist_backend": (dist.get_backend() if n > 1 and dist.is_initialized() else None),
             },
-            "roofline": roofline(prof, breakdown, W, H, a, n, ref_work, elapsed / a.steps * 1e3, NB),
+            "full": a.full,
             "traced_rays_per_frame": int(traced_rays),
             "traced_mrays_per_s": round(traced_rays * a.steps / elapsed / 1e6, 3),
             "rays_note": "value counts the reference's rays (one per World::intersect call, world.rs:71,101), "
                          "including shadow rays the fast path provably need not trace; traced_* counts what the "
                          "kernels traced",
-            "parity": parity,
         }
+        if a.dump_outputs:
+            out["dump_outputs"] = a.dump_outputs
+        if a.full:
+            out["roofline"] = roofline(prof, breakdown, W, H, a, n, ref_work, elapsed / a.steps * 1e3, NB)
+            out["parity"] = parity
         if split is not None:
             out["per_rank"] = split
-        if n == 1 and not a.no_end_to_end:
+        if a.full and n == 1 and not a.no_end_to_end:
             out["end_to_end"] = end_to_end(world, cam, depth, frames=10)
-        if n == 1 and a.config == "c3" and not a.no_distinct:
+        if a.full and n == 1 and a.config == "c3" and not a.no_distinct:
             out["distinct_cameras"] = distinct_cameras(world, depth, rstreams, dev, value)
-        if n == 1 and not a.no_cold:
+        if a.full and n == 1 and not a.no_cold:
             out["cold_ms"] = cold_start(local_rank)
-        if n == 1 and not a.no_cpu_baseline:
+        if a.full and n == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(world, cam, depth, a.cpu_seconds)
         print(json.dumps(out), flush=True)
     if parity is not None and not parity["ok"]:
@@ -736,6 +769,30 @@ def main():
         if hasattr(fa, "close"):
             fa.close()  # the per-stream RCCL communicators
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 60_000_000  # per run, all arrays together (the full C3 canvas: 49.8 MB)
+
+
+def dump_outputs(path, tensors, limit=DUMP_LIMIT_BYTES):
+    """Write each device tensor of `tensors` to path/<name>.npy as float64. An
+    array whose share of `limit` bytes is too small for it is written as a
+    fixed sample of its pixels (rows of its last axis; generator seeded with a
+    constant, indices ascending), so two builds given the same arguments write
+    the same pixels."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = limit // max(1, len(tensors))
+    for name, t in tensors.items():
+        if t is None:
+            raise SystemExit(f"bench.py: --dump-outputs: no {name} to write (no timed step?)")
+        arr = np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float64)
+        if arr.nbytes > share:
+            px = arr.reshape(-1, arr.shape[-1])
+            keep = share // (px.shape[1] * px.itemsize)
+            idx = np.sort(np.random.default_rng(0x5EED).choice(px.shape[0], size=keep, replace=False))
+            arr = px[idx]
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 def submit(fa, step, end):

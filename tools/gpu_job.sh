@@ -4,9 +4,9 @@
 # Usage (on the box): bash tools/gpu_job.sh TAG STEP [STEP ...]
 #   tests      pytest -m gpu (thread-timeout per test)
 #   smoke      __graft_entry__.smoke()
-#   bench      python bench.py (default args) > TAG_bench.json
-#   benchq     bench.py without the CPU baseline / end-to-end (quick)
-#   c5         bench.py --config c5 --steps 3 --warmup 1 (no CPU baseline)
+#   bench      python bench.py --full (default args) > TAG_bench.json
+#   benchq     bench.py --full without the CPU baseline / end-to-end (quick)
+#   c5         bench.py --full --config c5 --steps 4 --warmup 2 (no CPU baseline)
 #   shard      tools/shard_time.py --ns 1,2,4,8
 #   shardb     the same with 8-frame batches (rt_render_frames_device)
 #   tsel       pytest -m gpu of the files in $TESTS
@@ -37,16 +37,16 @@ for s in "$@"; do
   case $s in
     tests) step tests 900 python -u -m pytest tests -m gpu -x -v --timeout 240 --timeout-method thread -p no:cacheprovider || exit 1 ;;
     smoke) step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" || exit 1 ;;
-    bench) step bench 600 python bench.py || exit 1; grep '^{' "$OUT/bench.log" > "$OUT/bench.json" ;;
-    benchq) step benchq 400 python bench.py --no-cpu-baseline --no-end-to-end || exit 1; grep '^{' "$OUT/benchq.log" > "$OUT/benchq.json" ;;
-    c5) step c5 600 python bench.py --config c5 --steps 4 --warmup 2 --no-cpu-baseline --no-end-to-end || exit 1 ;;
+    bench) step bench 600 python bench.py --full || exit 1; grep '^{' "$OUT/bench.log" > "$OUT/bench.json" ;;
+    benchq) step benchq 400 python bench.py --full --no-cpu-baseline --no-end-to-end || exit 1; grep '^{' "$OUT/benchq.log" > "$OUT/benchq.json" ;;
+    c5) step c5 600 python bench.py --full --config c5 --steps 4 --warmup 2 --no-cpu-baseline --no-end-to-end || exit 1 ;;
     shard) step shard 600 python tools/shard_time.py --ns 1,2,4,8 --frames 100 --ranks || exit 1 ;;
     shardb) step shardb 600 python tools/shard_time.py --ns 1,2,4,8 --frames 160 --batch 8 --ranks || exit 1 ;;
     tsel) step tsel 600 python -u -m pytest $TESTS -m gpu -x -v --timeout 240 --timeout-method thread -p no:cacheprovider || exit 1 ;;
     trace) step trace 600 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o trace --output-format csv -- \
-             python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-end-to-end || exit 1 ;;
+             python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-end-to-end || exit 1 ;;
     trace_c5) step trace_c5 600 rocprofv3 --kernel-trace --stats -d "$OUT/trace_c5" -o trace_c5 --output-format csv -- \
-             python bench.py --config c5 --steps 3 --warmup 1 --no-cpu-baseline --no-end-to-end || exit 1 ;;
+             python bench.py --full --config c5 --steps 3 --warmup 1 --no-cpu-baseline --no-end-to-end || exit 1 ;;
     pmc) step pmc 900 bash tools/profile.sh "$TAG" || exit 1 ;;
     pmc_c5) BATCH=1 SUMMARY_ARGS="--width 4096 --height 4096 --spheres 9996" step pmc_c5 900 bash tools/profile.sh "${TAG}_c5" --config c5 --width 4096 --height 4096 --spheres 9996 || exit 1 ;;
     quick) step quick 600 python tools/quick_time.py || exit 1 ;;
