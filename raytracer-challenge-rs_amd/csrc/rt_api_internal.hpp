@@ -2,8 +2,8 @@
 // librtamd.so, hidden visibility; not part of include/rt_render.h):
 //   rt_api.cpp        errors, ABI sizes, pinned host buffers, camera / matrix, dev hooks
 //   rt_scene.cpp      rt_scene_create*: flattening, hierarchies, upload
-//   rt_workspace.cpp  the workspace pool's render call (run_render), overflow checks,
-//                     device-to-host copies
+//   rt_workspace.cpp  the workspace pool's render call (run_render, settle), overflow
+//                     checks, device-to-host copies
 //   rt_render.cpp     the render entry points (device shards, batches, host canvas,
 //                     PPM, ray batches)
 //   rt_multi.cpp      rt_render_multi and the RCCL hooks
@@ -287,14 +287,53 @@ int ensure_dev_buffer(double** buf, size_t* cap, size_t need);
 // work already on `st`; synchronous.
 int copy_to_host(rt_scene::HostCtx* s, int d2h, void* dst, const void* src, size_t n, hipStream_t st);
 int check_faults(rt_scene* s);
-int run_render(rt_scene* s, const DevCamera& cam, const double* d_rays, uint32_t n_tasks, uint32_t aa,
-               uint32_t max_depth, uint32_t row_block, uint32_t shard, uint32_t n_shards, double* d_out,
-               hipStream_t stream, DevStats* stats_out = nullptr, float* ms_out = nullptr, uint32_t flags = 0,
-               rt_scene::WfSlot** used = nullptr, const FrameTable* batch = nullptr, unsigned n_frames = 1,
-               bool sync = false, std::unique_lock<std::mutex>* lk = nullptr, bool count = false,
-               bool keep_pin = false, uint32_t blk_period = 0, uint64_t blk_mask = 0,
-               hipEvent_t gen_ev = nullptr, int gen_ev_g = -1, bool* gen_ev_recorded = nullptr,
-               WfSizing* sizing = nullptr);
+// A workspace that stays pinned to a call after run_render has returned
+// (RenderCall::keep_pin), for a caller that waits for the render on its own
+// terms: unpinned by settle(), or else on every return, under the scene's lock
+// (`lk`: the call's hold of s->mu, taken again if released; null: the guard
+// takes the lock itself).
+struct PinGuard {
+  rt_scene* s = nullptr;
+  std::unique_lock<std::mutex>* lk = nullptr;
+  rt_scene::WfSlot* w = nullptr;
+  PinGuard() = default;
+  PinGuard(rt_scene* s_, std::unique_lock<std::mutex>* lk_) : s(s_), lk(lk_) {}
+  PinGuard(const PinGuard&) = delete;
+  PinGuard& operator=(const PinGuard&) = delete;
+  ~PinGuard() {
+    if (!w) return;
+    if (lk && lk->owns_lock()) {
+      --w->pins;
+    } else {
+      std::lock_guard<std::mutex> own(s->mu);
+      --w->pins;
+    }
+  }
+};
+// How run_render runs a job; what a site does not mention keeps its default.
+struct RenderCall {
+  std::unique_lock<std::mutex>* lk;  // the scene's lock (held on entry and on return): waits run unlocked
+  explicit RenderCall(std::unique_lock<std::mutex>* lk_ = nullptr) : lk(lk_) {}
+  uint32_t flags = 0;          // the public call's RT_RENDER_* flags
+  bool sync = false;           // wait for the render; a frame that overflowed is rendered again until it fits
+  bool stats = false;          // RenderResult::stats (a counted render; implies sync)
+  bool time = false;           // RenderResult::ms (implies sync)
+  bool count = false;          // count the reference's rays without synchronising (Wavefront::read_stats later)
+  PinGuard* keep_pin = nullptr;  // the workspace stays pinned after the return, in this guard
+  WfSizing* sizing = nullptr;  // the arena sizes to use and teach (default: the scene's)
+};
+struct RenderResult {
+  DevStats stats{};
+  float ms = 0.f;                // kernel time
+  bool gen_ev_recorded = false;  // the job's early event was recorded (WfJob::gen_ev)
+};
+int run_render(rt_scene* s, const WfJob& job, hipStream_t stream, const RenderCall& call, RenderResult* res = nullptr);
+// After the caller has waited for the render of a workspace it kept pinned
+// (under the scene's lock): the sizes it learned go to `sz`, its overflow
+// record is taken (`over`: the frame is incomplete, the arenas have grown) and
+// it is unpinned. A guard without a workspace (an empty render) settles as not
+// overflowed.
+int settle(PinGuard& pin, WfSizing& sz, bool* over);
 void fill_stats(rt_stats* st, const DevStats& ds, float ms_kernel, double ms_total);
 void add_stats(DevStats& sum, const DevStats& ds);
 
@@ -326,11 +365,9 @@ inline DevCamera to_dev_camera(const rt_camera_desc& c) {
   return d;
 }
 
-inline bool valid_aa(uint32_t aa) { return aa == 1 || aa == 2 || aa == 4 || aa == 8 || aa == 16; }
-
-inline bool valid_pattern(uint32_t period, uint64_t mask) {
-  return period >= 1 && period <= 64 && mask != 0 && (period == 64 || (mask >> period) == 0);
-}
+// what the entry points check before they build a job: the job's own rules (rt_wavefront.hpp)
+inline bool valid_aa(uint32_t aa) { return wf_aa_valid(aa); }
+inline bool valid_pattern(uint32_t period, uint64_t mask) { return period >= 1 && wf_pattern_valid(period, mask); }
 
 // A host context for the duration of one entry point (rt_scene::HostCtx),
 // returned to the pool under the scene's lock.

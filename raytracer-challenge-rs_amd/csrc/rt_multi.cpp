@@ -88,11 +88,12 @@ struct HostReg {
 // device into a device buffer of its rows, then copied into the canvas rows
 // it owns: one 2-D copy for its full blocks (n_shards * row_block rows apart
 // in the canvas), one more for a short last block. `host_ready`: the canvas is
-// pinned or registered for every device. Synchronous; an overflowed render is
-// rendered again inside run_render.
+// pinned or registered for every device. Synchronous (RenderCall::sync: an
+// overflowed render is rendered again inside run_render). `res`, when given,
+// receives the shard's counters and kernel time.
 int render_shard_to_host(rt_scene* s, const rt_camera_desc& cam, uint32_t max_depth, uint32_t aa,
                          uint32_t row_block, uint32_t shard, uint32_t n_shards, double* out_rgb, bool host_ready,
-                         DevStats* ds, float* ms) {
+                         RenderResult* res) {
   std::unique_lock<std::mutex> lk(s->mu);
   RT_DEVICE(s->device);
   const uint32_t W = cam.hsize, H = cam.vsize;
@@ -102,7 +103,7 @@ int render_shard_to_host(rt_scene* s, const rt_camera_desc& cam, uint32_t max_de
   RT_TAKE_CTX(cx);
   rt_scene::HostCtx* c = cx.c;
   const uint64_t n_pix = (uint64_t)W * H;
-  if (n_shards == 1 && !ds && s->tune.bands > 1 && fast_path(s) && n_pix * aa >= ((uint64_t)1 << 20)) {
+  if (n_shards == 1 && !res && s->tune.bands > 1 && fast_path(s) && n_pix * aa >= ((uint64_t)1 << 20)) {
     int rc = ensure_dev_buffer(&c->d_out, &c->out_cap, n_pix * 3);
     if (rc != RT_OK) return rc;
     rc = render_banded(s, lk, c, cam, max_depth, aa, out_rgb, host_ready);
@@ -110,8 +111,11 @@ int render_shard_to_host(rt_scene* s, const rt_camera_desc& cam, uint32_t max_de
   }
   int rc = ensure_dev_buffer(&c->d_out, &c->out_cap, (size_t)rows * W * 3);
   if (rc != RT_OK) return rc;
-  rc = run_render(s, to_dev_camera(cam), nullptr, rows * W * aa, aa, max_depth, row_block, shard, n_shards, c->d_out,
-                  c->stream, ds, ms, 0, nullptr, nullptr, 1, true, &lk);
+  RenderCall call(&lk);
+  call.sync = true;
+  call.stats = call.time = res != nullptr;
+  rc = run_render(s, WfJob::camera_shard(to_dev_camera(cam), rows * W * aa, aa, max_depth, c->d_out, row_block, shard,
+                                         n_shards), c->stream, call, res);
   if (rc != RT_OK) return rc;
   lk.unlock();  // the context is this call's
   if (!host_ready)  // (a canvas the DMA engine cannot write: the staged copy of rt_render, rows in shard order)
@@ -192,19 +196,8 @@ int render_multi_gather(rt_scene* const* scenes, int n_devices, const rt_camera_
   // every device renders its shard (asynchronously, each on its scene's stream); the
   // workspaces this call renders on stay pinned until it has read their overflow
   // records (no other call takes them over, and no other call's records are read)
-  std::vector<rt_scene::WfSlot*> used(n_devices, nullptr);
-  auto unpin_all = [&]() {
-    for (int i = 0; i < n_devices; ++i)
-      if (used[i]) {
-        std::lock_guard<std::mutex> lk(scenes[i]->mu);
-        --used[i]->pins;
-        used[i] = nullptr;
-      }
-  };
-  struct Unpin {
-    decltype(unpin_all)& f;
-    ~Unpin() { f(); }
-  } unpin_on_return{unpin_all};
+  std::deque<PinGuard> pins;  // (each takes its scene's lock itself: this call holds none across its waits)
+  for (int i = 0; i < n_devices; ++i) pins.emplace_back(scenes[i], nullptr);
   // every stream this call enqueued on drains before any return (the canvas is the caller's)
   struct Drain {
     rt_scene* const* sc;
@@ -214,86 +207,76 @@ int render_multi_gather(rt_scene* const* scenes, int n_devices, const rt_camera_
         if (hipSetDevice(i) == hipSuccess && hipStreamSynchronize(sc[i]->stream) != hipSuccess) (void)hipGetLastError();
     }
   } drain{scenes, n_devices};
-  int attempt = 0;
-render_all:
-  for (int i = 0; i < n_devices; ++i) {
-    RT_HIP(hipSetDevice(i));
-    std::lock_guard<std::mutex> lk(scenes[i]->mu);
-    const uint32_t rows = rt_shard_rows(H, row_block, i, n_devices);
-    if (stats) RT_HIP(hipEventRecord(mc.ev0[i], scenes[i]->stream));
-    rc = run_render(scenes[i], to_dev_camera(*camera), nullptr, rows * W * aa_samples, aa_samples, max_depth,
-                    row_block, i, n_devices, mc.send[i], scenes[i]->stream, nullptr, nullptr, 0, &used[i], nullptr,
-                    1, false, nullptr, stats != nullptr, true);
-    if (rc != RT_OK) return rc;
-    if (stats) RT_HIP(hipEventRecord(mc.ev1[i], scenes[i]->stream));
-  }
-  {
-    if (ncclGroupStart() != ncclSuccess) return fail(RT_ERR_RCCL, "ncclGroupStart");
-    for (int i = 0; i < n_devices; ++i)
-      if (ncclGather(mc.send[i], i == 0 ? mc.recv : nullptr, per, ncclDouble, 0, mc.comms[i], scenes[i]->stream) !=
-          ncclSuccess) {
-        (void)ncclGroupEnd();
-        return fail(RT_ERR_RCCL, "ncclGather");
-      }
-    if (ncclGroupEnd() != ncclSuccess) return fail(RT_ERR_RCCL, "ncclGroupEnd");
-  }
-  // device 0 holds every shard, rank-major: copy each row block straight into its canvas rows
-  RT_HIP(hipSetDevice(0));
-  for (int i = 0; i < n_devices; ++i) {
-    uint32_t lr = 0;
-    for (uint32_t blk = (uint32_t)i; (uint64_t)blk * row_block < H; blk += (uint32_t)n_devices) {
-      const uint32_t y0 = blk * row_block, nr = std::min(row_block, H - y0);
-      RT_HIP(hipMemcpyAsync(out_rgb + (size_t)y0 * W * 3, mc.recv + (size_t)i * per + (size_t)lr * W * 3,
-                            (size_t)nr * W * 3 * sizeof(double), hipMemcpyDeviceToHost, scenes[0]->stream));
-      lr += nr;
-    }
-  }
-  for (int i = 0; i < n_devices; ++i) {
-    RT_HIP(hipSetDevice(i));
-    RT_HIP(hipStreamSynchronize(scenes[i]->stream));
-  }
-  // a shard that overflowed its queue arenas (this call's workspaces only): the arenas
-  // have grown, render the frame again
-  bool again = false;
-  for (int i = 0; i < n_devices; ++i) {
-    if (!used[i]) continue;  // an empty shard
-    RT_HIP(hipSetDevice(i));
-    std::lock_guard<std::mutex> lk(scenes[i]->mu);
-    bool was = false;
-    used[i]->wf->learn(scenes[i]->sizing);
-    RT_HIP(used[i]->wf->take_overflow(&was));
-    again = again || was;
-  }
-  if (again) {
-    if (++attempt > 24) return fail(RT_ERR_HIP, "wavefront queue arenas: the frame does not fit");
-    unpin_all();  // (the counters are read from the last attempt's workspaces)
-    goto render_all;
-  }
-  if (stats) {
-    std::memset(stats, 0, sizeof *stats);
+  for (int attempt = 0;; ++attempt) {
     for (int i = 0; i < n_devices; ++i) {
-      if (!used[i]) continue;  // an empty shard
       RT_HIP(hipSetDevice(i));
       std::lock_guard<std::mutex> lk(scenes[i]->mu);
-      DevStats ds{};
-      RT_HIP(used[i]->wf->read_stats(&ds));
-      rt_stats x;
-      fill_stats(&x, ds, 0.f, 0.0);
-      stats->rays_primary += x.rays_primary; stats->rays_reflect += x.rays_reflect;
-      stats->rays_refract += x.rays_refract; stats->rays_shadow += x.rays_shadow;
-      stats->sphere_tests += x.sphere_tests; stats->plane_tests += x.plane_tests;
-      stats->other_tests += x.other_tests;
-      stats->sphere_disc_ge0 = x.exhaustive ? stats->sphere_disc_ge0 + x.sphere_disc_ge0 : x.sphere_disc_ge0;
-      stats->rays_shadow_traced += x.rays_shadow_traced;
-      stats->sphere_tests_executed += x.sphere_tests_executed;
-      stats->box_tests_executed += x.box_tests_executed;
-      float ms = 0.f;  // ms_kernel: the slowest device's shard render (HIP events around it)
-      RT_HIP(hipEventElapsedTime(&ms, mc.ev0[i], mc.ev1[i]));
-      stats->ms_kernel = std::max(stats->ms_kernel, (double)ms);
+      const uint32_t rows = rt_shard_rows(H, row_block, i, n_devices);
+      if (stats) RT_HIP(hipEventRecord(mc.ev0[i], scenes[i]->stream));
+      RenderCall call;
+      call.count = stats != nullptr;
+      call.keep_pin = &pins[i];
+      rc = run_render(scenes[i], WfJob::camera_shard(to_dev_camera(*camera), rows * W * aa_samples, aa_samples,
+                                                     max_depth, mc.send[i], row_block, i, n_devices),
+                      scenes[i]->stream, call);
+      if (rc != RT_OK) return rc;
+      if (stats) RT_HIP(hipEventRecord(mc.ev1[i], scenes[i]->stream));
     }
-    stats->ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    {
+      if (ncclGroupStart() != ncclSuccess) return fail(RT_ERR_RCCL, "ncclGroupStart");
+      for (int i = 0; i < n_devices; ++i)
+        if (ncclGather(mc.send[i], i == 0 ? mc.recv : nullptr, per, ncclDouble, 0, mc.comms[i], scenes[i]->stream) !=
+            ncclSuccess) {
+          (void)ncclGroupEnd();
+          return fail(RT_ERR_RCCL, "ncclGather");
+        }
+      if (ncclGroupEnd() != ncclSuccess) return fail(RT_ERR_RCCL, "ncclGroupEnd");
+    }
+    // device 0 holds every shard, rank-major: copy each row block straight into its canvas rows
+    RT_HIP(hipSetDevice(0));
+    for (int i = 0; i < n_devices; ++i) {
+      uint32_t lr = 0;
+      for (uint32_t blk = (uint32_t)i; (uint64_t)blk * row_block < H; blk += (uint32_t)n_devices) {
+        const uint32_t y0 = blk * row_block, nr = std::min(row_block, H - y0);
+        RT_HIP(hipMemcpyAsync(out_rgb + (size_t)y0 * W * 3, mc.recv + (size_t)i * per + (size_t)lr * W * 3,
+                              (size_t)nr * W * 3 * sizeof(double), hipMemcpyDeviceToHost, scenes[0]->stream));
+        lr += nr;
+      }
+    }
+    for (int i = 0; i < n_devices; ++i) {
+      RT_HIP(hipSetDevice(i));
+      RT_HIP(hipStreamSynchronize(scenes[i]->stream));
+    }
+    // every shard's workspace read back under its scene's lock: its counters, then settle() (its
+    // learned sizes and overflow record; unpinned). A shard that overflowed its queue arenas
+    // (this call's workspaces only): the arenas have grown, render the frame again
+    bool again = false;
+    DevStats sum{};
+    float ms_kernel = 0.f;  // the slowest device's shard render (HIP events around it)
+    for (int i = 0; i < n_devices; ++i) {
+      if (!pins[i].w) continue;  // an empty shard
+      RT_HIP(hipSetDevice(i));
+      std::lock_guard<std::mutex> lk(scenes[i]->mu);
+      if (stats) {
+        DevStats ds{};
+        RT_HIP(pins[i].w->wf->read_stats(&ds));
+        add_stats(sum, ds);
+        float ms = 0.f;
+        RT_HIP(hipEventElapsedTime(&ms, mc.ev0[i], mc.ev1[i]));
+        ms_kernel = std::max(ms_kernel, ms);
+      }
+      bool was = false;
+      if ((rc = settle(pins[i], scenes[i]->sizing, &was)) != RT_OK) return rc;
+      again = again || was;
+    }
+    if (!again) {
+      if (stats)
+        fill_stats(stats, sum, ms_kernel,
+                   std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+      return RT_OK;
+    }
+    if (attempt >= 24) return fail(RT_ERR_HIP, "wavefront queue arenas: the frame does not fit");
   }
-  return RT_OK;
 }
 
 }  // namespace
@@ -395,16 +378,14 @@ int rt_render_multi(rt_scene* const* scenes, int n_devices, const rt_camera_desc
   struct Shard {
     int rc = RT_OK;
     std::string err;
-    DevStats ds{};
-    float ms = 0.f;
+    RenderResult r;
   };
   std::vector<Shard> res((size_t)n_devices);
   auto work = [&](int i) {
     Shard& r = res[(size_t)i];
     r.rc = guarded([&]() -> int {
       return render_shard_to_host(scenes[i], *camera, max_depth, aa_samples, row_block, (uint32_t)i,
-                                  (uint32_t)n_devices, out_rgb, host_ready, stats ? &r.ds : nullptr,
-                                  stats ? &r.ms : nullptr);
+                                  (uint32_t)n_devices, out_rgb, host_ready, stats ? &r.r : nullptr);
     });
     if (r.rc != RT_OK) r.err = g_err;  // (this thread's message)
   };
@@ -425,8 +406,8 @@ int rt_render_multi(rt_scene* const* scenes, int n_devices, const rt_camera_desc
     DevStats sum{};
     float ms = 0.f;  // ms_kernel: the slowest device's shard render
     for (const Shard& r : res) {
-      add_stats(sum, r.ds);
-      ms = std::max(ms, r.ms);
+      add_stats(sum, r.r.stats);
+      ms = std::max(ms, r.r.ms);
     }
     fill_stats(stats, sum, ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
   }
@@ -450,12 +431,11 @@ int rtamd_render_shard_host(const rt_scene* scene, const rt_camera_desc* camera,
   rt_scene* s = const_cast<rt_scene*>(scene);
   const auto t0 = std::chrono::steady_clock::now();
   const HostReg reg(out_rgb, (size_t)camera->hsize * camera->vsize * 3 * sizeof(double), s->device);
-  DevStats ds{};
-  float ms = 0.f;
+  RenderResult r;
   const int rc = render_shard_to_host(s, *camera, max_depth, aa_samples, row_block, shard, n_shards, out_rgb,
-                                      reg.ready, stats ? &ds : nullptr, stats ? &ms : nullptr);
+                                      reg.ready, stats ? &r : nullptr);
   if (rc == RT_OK && stats)
-    fill_stats(stats, ds, ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    fill_stats(stats, r.stats, r.ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
   return rc;
   });
 }

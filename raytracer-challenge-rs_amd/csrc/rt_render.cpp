@@ -34,14 +34,16 @@ int rt_render_shard_device_ex(const rt_scene* scene, const rt_camera_desc* camer
   const uint64_t n_tasks = (uint64_t)rows * camera->hsize * aa_samples;
   if (n_tasks >= (1ull << 31)) return fail(RT_ERR_INVALID_ARGUMENT, "shard too large");
   hipStream_t st = (hipStream_t)stream;  // NULL = the default stream (torch's current stream is often 0)
-  DevStats ds{};
-  float ms = 0.f;
-  int rc = run_render(s, to_dev_camera(*camera), nullptr, (uint32_t)n_tasks, aa_samples, max_depth, row_block, shard,
-                      n_shards, d_out_rgb, st, stats ? &ds : nullptr, stats ? &ms : nullptr, flags, nullptr, nullptr,
-                      1, false, &lk);
+  RenderCall call(&lk);
+  call.flags = flags;
+  call.stats = call.time = stats != nullptr;
+  RenderResult r;
+  int rc = run_render(s, WfJob::camera_shard(to_dev_camera(*camera), (uint32_t)n_tasks, aa_samples, max_depth,
+                                             d_out_rgb, row_block, shard, n_shards), st, call, &r);
   if (rc != RT_OK) return rc;
   if (stats)
-    fill_stats(stats, ds, ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    fill_stats(stats, r.stats, r.ms,
+               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
   return RT_OK;
   });
 }
@@ -87,6 +89,9 @@ int render_frames(const rt_scene* scene, const rt_camera_desc* cameras, uint32_t
   // a pass holds at most ~2^25 root rays (16 C3 frames; 2 C5 frames), which bounds the
   // workspace's queues; larger frames gain nothing from sharing launches
   const uint32_t per_pass = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(kMaxFrames, ((uint64_t)1 << 25) / std::max<uint64_t>(padded, 1)));
+  RenderCall call(&lk);
+  call.flags = flags;
+  call.stats = call.time = stats != nullptr;
   for (uint32_t f0 = 0; f0 < n_frames;) {
     const uint32_t nf = batch ? std::min<uint32_t>(per_pass, n_frames - f0) : 1u;
     FrameTable tab{};
@@ -94,15 +99,18 @@ int render_frames(const rt_scene* scene, const rt_camera_desc* cameras, uint32_t
       tab.cam[f] = to_dev_camera(cameras[f0 + f]);
       tab.out[f] = d_out_rgb[f0 + f];
     }
-    DevStats ds{};
-    float ms = 0.f;
-    int rc = run_render(s, tab.cam[0], nullptr, (uint32_t)per, aa_samples, max_depth, row_block, shard, n_shards,
-                        tab.out[0], st, stats ? &ds : nullptr, stats ? &ms : nullptr, flags, nullptr,
-                        nf > 1 ? &tab : nullptr, nf, false, &lk, false, false, blk_period, blk_mask);
+    WfJob job = WfJob::camera_shard(tab.cam[0], (uint32_t)per, aa_samples, max_depth, tab.out[0], row_block, shard,
+                                    n_shards);
+    job.blk_period = blk_period;
+    job.blk_mask = blk_mask;
+    if (nf > 1) job.batch = &tab;
+    job.n_frames = nf;
+    RenderResult r;
+    int rc = run_render(s, job, st, call, &r);
     if (rc != RT_OK) return rc;
     if (stats) {
-      add_stats(sum, ds);
-      ms_sum += ms;
+      add_stats(sum, r.stats);
+      ms_sum += r.ms;
     }
     f0 += nf;
   }
@@ -192,23 +200,27 @@ struct BandRender {
   rt_scene::HostCtx* c;
   const BandPlan& p;
   hipStream_t st[kMaxBands] = {};
-  rt_scene::WfSlot* used[kMaxBands] = {};
+  PinGuard pins[kMaxBands];  // (destroyed after the destructor's body: unpinned once the streams have drained)
   int n_enq = 0;  // band streams with work enqueued
   BandRender(rt_scene* s_, std::unique_lock<std::mutex>& lk_, rt_scene::HostCtx* c_, const BandPlan& p_)
-      : s(s_), lk(lk_), c(c_), p(p_) {}
+      : s(s_), lk(lk_), c(c_), p(p_) {
+    for (PinGuard& g : pins) {
+      g.s = s;
+      g.lk = &lk;
+    }
+  }
   ~BandRender() {
     for (int k = 0; k < n_enq; ++k)
       if (hipStreamSynchronize(st[k]) != hipSuccess) (void)hipGetLastError();
     if (!lk.owns_lock()) lk.lock();
-    for (int k = 0; k < p.bands; ++k) unpin(k);
   }
   BandRender(const BandRender&) = delete;
   BandRender& operator=(const BandRender&) = delete;
-  void unpin(int k) {
-    if (used[k]) {
-      --used[k]->pins;
-      used[k] = nullptr;
-    }
+  // band k's job (a block pattern over the whole canvas)
+  WfJob job(int k, const DevCamera& dc, uint32_t W, uint32_t aa, uint32_t max_depth) const {
+    const uint32_t rows = p.y0[k + 1] - p.y0[k];
+    return WfJob::block_pattern(dc, rows * W * aa, aa, max_depth, c->d_out + (size_t)p.y0[k] * W * 3, p.rb, p.nb,
+                                p.mask[k]);
   }
   int open() {
     st[0] = c->stream;
@@ -223,15 +235,19 @@ struct BandRender {
   // enqueues band k's render (under the scene's lock)
   int render(int k, const DevCamera& dc, uint32_t W, uint32_t aa, uint32_t max_depth) {
     if (k > 0) RT_HIP(hipStreamWaitEvent(st[k], c->band_ev[k - 1], 0));  // band k after band k-1's render
-    const uint32_t rows = p.y0[k + 1] - p.y0[k];
-    const bool early = s->tune.band_gen >= 0 && k + 1 < p.bands;
-    bool recorded = false;
+    WfJob j = job(k, dc, W, aa, max_depth);
+    if (s->tune.band_gen >= 0 && k + 1 < p.bands) {  // band k+1 may start early
+      j.gen_ev = c->band_ev[k];
+      j.gen_ev_g = s->tune.band_gen;
+    }
+    RenderCall call(&lk);
+    call.keep_pin = &pins[k];
+    call.sizing = &s->band_sizing;
+    RenderResult r;
     n_enq = k + 1;
-    int rc = run_render(s, dc, nullptr, rows * W * aa, aa, max_depth, p.rb, 0, 1, c->d_out + (size_t)p.y0[k] * W * 3,
-                        st[k], nullptr, nullptr, 0, &used[k], nullptr, 1, false, &lk, false, true, p.nb, p.mask[k],
-                        early ? c->band_ev[k] : nullptr, s->tune.band_gen, &recorded, &s->band_sizing);
+    int rc = run_render(s, j, st[k], call, &r);
     if (rc != RT_OK) return rc;
-    if (!recorded) RT_HIP(hipEventRecord(c->band_ev[k], st[k]));
+    if (!r.gen_ev_recorded) RT_HIP(hipEventRecord(c->band_ev[k], st[k]));
     return RT_OK;
   }
   // every band stream drained (the scene's lock released meanwhile); the first error
@@ -244,15 +260,6 @@ struct BandRender {
     }
     lk.lock();
     if (first != hipSuccess) return fail(RT_ERR_HIP, std::string("banded render: ") + hipGetErrorString(first));
-    return RT_OK;
-  }
-  // after wait_all: band k's workspace read back (learned sizes, overflow) and unpinned
-  int overflowed(int k, bool* over) {
-    *over = false;
-    if (!used[k]) return RT_OK;
-    used[k]->wf->learn(s->band_sizing);
-    RT_HIP(used[k]->wf->take_overflow(over));
-    unpin(k);
     return RT_OK;
   }
 };
@@ -308,14 +315,13 @@ int render_banded(rt_scene* s, std::unique_lock<std::mutex>& lk, rt_scene::HostC
   if ((rc = br.wait_all()) != RT_OK) return rc;
   for (int k = 0; k < p.bands; ++k) {
     bool over = false;
-    if ((rc = br.overflowed(k, &over)) != RT_OK) return rc;
+    if ((rc = settle(br.pins[k], s->band_sizing, &over)) != RT_OK) return rc;
     if (!over) continue;
     // (its canvas rows are NaN: render the band again, synchronously, with the arenas grown)
-    const uint32_t rows = p.y0[k + 1] - p.y0[k];
-    rc = run_render(s, dc, nullptr, rows * W * aa, aa, max_depth, p.rb, 0, 1, c->d_out + (size_t)p.y0[k] * W * 3,
-                    br.st[k], nullptr, nullptr, 0, nullptr, nullptr, 1, true, &lk, false, false, p.nb, p.mask[k],
-                    nullptr, -1, nullptr, &s->band_sizing);
-    if (rc != RT_OK) return rc;
+    RenderCall again(&lk);
+    again.sync = true;
+    again.sizing = &s->band_sizing;
+    if ((rc = run_render(s, br.job(k, dc, W, aa, max_depth), br.st[k], again)) != RT_OK) return rc;
     if ((rc = copy(k)) != RT_OK) return rc;
     lk.unlock();
     const hipError_t e = hipStreamSynchronize(br.st[k]);
@@ -357,18 +363,21 @@ int rt_render_ex(const rt_scene* scene, const rt_camera_desc* camera, uint32_t m
     rc = render_banded(s, lk, cx.c, *camera, max_depth, aa_samples, out_rgb);
     if (rc != RT_ERR_NO_DEVICE) return rc;  // (RT_ERR_NO_DEVICE: not bandable, render it whole below)
   }
-  DevStats ds{};
-  float ms = 0.f;
-  rc = run_render(s, to_dev_camera(*camera), nullptr, (uint32_t)(n_pix * aa_samples), aa_samples, max_depth,
-                  camera->vsize, 0, 1, cx.c->d_out, cx.c->stream, stats ? &ds : nullptr, &ms, flags, nullptr, nullptr,
-                  1, true, &lk);
+  RenderCall call(&lk);
+  call.flags = flags;
+  call.stats = stats != nullptr;
+  call.time = true;
+  RenderResult r;
+  rc = run_render(s, WfJob::camera_shard(to_dev_camera(*camera), (uint32_t)(n_pix * aa_samples), aa_samples, max_depth,
+                                         cx.c->d_out, camera->vsize), cx.c->stream, call, &r);
   if (rc != RT_OK) return rc;
   const int d2h = s->tune.d2h;
   lk.unlock();  // the copy to the caller's canvas runs unlocked (the context is this call's)
   if ((rc = copy_to_host(cx.c, d2h, out_rgb, cx.c->d_out, n_pix * 3 * sizeof(double), cx.c->stream)) != RT_OK)
     return rc;
   if (stats)
-    fill_stats(stats, ds, ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    fill_stats(stats, r.stats, r.ms,
+               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
   return RT_OK;
   });
 }
@@ -417,27 +426,17 @@ int rt_render_ppm(const rt_scene* scene, const rt_camera_desc* camera, uint32_t 
       if (hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
     }
   } drain{c->stream};
-  DevStats ds{};
-  float ms = 0.f;
-  const DevCamera dc = to_dev_camera(*camera);
-  const uint32_t n_tasks = (uint32_t)(n_pix * aa_samples);
+  const WfJob job = WfJob::camera_shard(to_dev_camera(*camera), (uint32_t)(n_pix * aa_samples), aa_samples, max_depth,
+                                        c->d_out, H);
   // The render, the encoder and the text's length in one pass of the stream: the host waits
   // once, then reads the workspace's overflow record; a frame that outgrew its arenas is
   // rendered again synchronously (with stats the render is synchronous anyway).
-  rt_scene::WfSlot* used = nullptr;
-  struct Unpin {
-    rt_scene::WfSlot*& w;
-    std::unique_lock<std::mutex>& lk;
-    ~Unpin() {
-      if (!w) return;
-      if (!lk.owns_lock()) lk.lock();
-      --w->pins;
-    }
-  } unpin{used, lk};
-  rc = run_render(s, dc, nullptr, n_tasks, aa_samples, max_depth, H, 0, 1, c->d_out, c->stream, stats ? &ds : nullptr,
-                  stats ? &ms : nullptr, 0, stats ? nullptr : &used, nullptr, 1, stats != nullptr, &lk, false,
-                  stats == nullptr);
-  if (rc != RT_OK) return rc;
+  PinGuard pin(s, &lk);
+  RenderCall call(&lk);
+  call.stats = call.time = stats != nullptr;
+  if (!stats) call.keep_pin = &pin;
+  RenderResult r;
+  if ((rc = run_render(s, job, c->stream, call, &r)) != RT_OK) return rc;
   auto encode = [&]() -> int {
     RT_HIP(ppm_encode_device(c->d_out, W, H, c->d_ppm, c->ppm_cap, (unsigned*)c->d_ppm_rows, d_off, hd, c->stream));
     RT_HIP(hipMemcpyAsync(c->h_len, d_off + H, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
@@ -448,18 +447,13 @@ int rt_render_ppm(const rt_scene* scene, const rt_camera_desc* camera, uint32_t 
     return RT_OK;
   };
   if ((rc = encode()) != RT_OK) return rc;
-  if (used) {
-    used->wf->learn(s->sizing);
-    bool over = false;
-    RT_HIP(used->wf->take_overflow(&over));
-    --used->pins;
-    used = nullptr;
-    if (over) {  // (the canvas was poisoned: render it again, growing the arenas until it fits)
-      rc = run_render(s, dc, nullptr, n_tasks, aa_samples, max_depth, H, 0, 1, c->d_out, c->stream, nullptr, nullptr,
-                      0, nullptr, nullptr, 1, true, &lk);
-      if (rc != RT_OK) return rc;
-      if ((rc = encode()) != RT_OK) return rc;
-    }
+  bool over = false;
+  if ((rc = settle(pin, s->sizing, &over)) != RT_OK) return rc;
+  if (over) {  // (the canvas was poisoned: render it again, growing the arenas until it fits)
+    RenderCall again(&lk);
+    again.sync = true;
+    if ((rc = run_render(s, job, c->stream, again)) != RT_OK) return rc;
+    if ((rc = encode()) != RT_OK) return rc;
   }
   const int d2h = s->tune.d2h;
   lk.unlock();
@@ -469,7 +463,8 @@ int rt_render_ppm(const rt_scene* scene, const rt_camera_desc* camera, uint32_t 
     if ((rc = copy_to_host(c, d2h, out, c->d_ppm, *out_len, c->stream)) != RT_OK) return rc;
   }
   if (stats)
-    fill_stats(stats, ds, ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    fill_stats(stats, r.stats, r.ms,
+               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
   return RT_OK;
   });
 }
@@ -534,17 +529,19 @@ int rt_color_at_batch_ex(const rt_scene* scene, const double* rays, size_t n, ui
   rc = ensure_dev_buffer(&c->d_out, &c->out_cap, n * 3);
   if (rc != RT_OK) return rc;
   if (n) RT_HIP(hipMemcpyAsync(c->d_in, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  DevCamera cam{};
-  DevStats ds{};
-  float ms = 0.f;
-  rc = run_render(s, cam, c->d_in, (uint32_t)n, 1, remaining, 1, 0, 1, c->d_out, c->stream, stats ? &ds : nullptr,
-                  &ms, flags, nullptr, nullptr, 1, true, &lk);
+  RenderCall call(&lk);
+  call.flags = flags;
+  call.stats = stats != nullptr;
+  call.time = true;
+  RenderResult r;
+  rc = run_render(s, WfJob::ray_batch(c->d_in, (uint32_t)n, remaining, c->d_out), c->stream, call, &r);
   if (rc != RT_OK) return rc;
   lk.unlock();
   if (n) RT_HIP(hipMemcpyAsync(out_rgb, c->d_out, n * 3 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   RT_HIP(hipStreamSynchronize(c->stream));
   if (stats)
-    fill_stats(stats, ds, ms, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    fill_stats(stats, r.stats, r.ms,
+               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
   return RT_OK;
   });
 }

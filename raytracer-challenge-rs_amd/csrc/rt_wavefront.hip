@@ -459,25 +459,36 @@ static hipError_t launch_fused(const DevScene& sc, const DevCamera& cam, const W
                : launch_fused_q<false, false>(sc, cam, a, primary, n, stream, tn);
 }
 
-hipError_t Wavefront::render(const DevScene& sc, const DevCamera& cam, bool camera_mode, const double* d_in_rays,
-                             unsigned n0, unsigned aa, unsigned max_depth, unsigned row_block, unsigned shard,
-                             unsigned n_shards, double* d_out, hipStream_t stream, WfSizing& sz, DevStats* stats,
-                             float* ms_kernel, const WfTuning& tn, bool solo, unsigned flags,
-                             const FrameTable* batch, unsigned n_frames, unsigned blk_period,
-                             unsigned long long blk_mask) {
-  if (max_depth + 2 > (unsigned)kMaxGen) return hipErrorInvalidValue;
-  if (blk_period > 64 || (blk_period && (blk_mask == 0 || (blk_period < 64 && (blk_mask >> blk_period) != 0))))
-    return hipErrorInvalidValue;
-  blk_period_ = blk_period;
-  blk_mask_ = blk_period ? blk_mask : 0ull;
-  if (aa == 0 || aa > 16 || (aa & (aa - 1)) != 0 || (!camera_mode && aa != 1) || n0 % aa != 0)
-    return hipErrorInvalidValue;
-  if (n_frames == 0 || n_frames > kMaxFrames || (n_frames > 1 && !batch)) return hipErrorInvalidValue;
+// The launch arguments every launch of a pass shares: the job's tiling and
+// batch, and this workspace's counters, primary records and frame table.
+// n0 / frame_real as in render_fast (the exhaustive pipeline: both job.n0).
+WfArgs Wavefront::job_args(const WfJob& job, unsigned n0, unsigned frame_real) const {
+  WfArgs a{};
+  a.aa = job.aa;
+  a.rows = frame_real / job.aa / (job.cam.hsize ? job.cam.hsize : 1);
+  a.n_frames = job.n_frames; a.frame_rays = n0 / job.n_frames; a.frame_real = frame_real; a.frames = d_frames_;
+  a.cnt = d_cnt_;
+  a.prim = d_prim_;
+  a.max_depth = job.max_depth;
+  a.camera_mode = job.camera_mode() ? 1u : 0u;
+  a.row_block = job.row_block; a.shard = job.shard; a.n_shards = job.n_shards;
+  a.blk_period = job.blk_period; a.blk_mask = job.blk_period ? job.blk_mask : 0ull;
+  return a;
+}
+
+hipError_t Wavefront::render(const DevScene& sc, const WfJob& job, hipStream_t stream, WfSizing& sz,
+                             const WfTuning& tn, bool solo) {
+  if (!wf_job_valid(job)) return hipErrorInvalidValue;
+  const DevCamera& cam = job.cam;
+  const bool camera_mode = job.camera_mode();
+  const unsigned max_depth = job.max_depth, n_frames = job.n_frames, flags = job.flags;
+  unsigned n0 = job.n0;
+  gen_ev_done_ = false;
   WF_CHECK(ensure_misc((size_t)sc.n_diag, n_frames));
   // BVH traversal (fused generations) and skipped shadow rays unless the
-  // reference's every-shape loop is asked for; counting (stats) never changes the algorithm
+  // reference's every-shape loop is asked for; counting never changes the algorithm
   const bool exhaustive = (flags & WF_EXHAUSTIVE) != 0;
-  const bool count = stats != nullptr || (flags & WF_COUNT) != 0;
+  const bool count = (flags & WF_COUNT) != 0;
   const bool bvh = tn.accel != 0 && !exhaustive && (sc.n_bvh > 0 || sc.n_obvh > 0 || sc.n_lbvh > 0);
   const bool fused = bvh;
   // (a counted render of a scene with groups traces every shadow ray: the reference's shape
@@ -499,11 +510,11 @@ hipError_t Wavefront::render(const DevScene& sc, const DevCamera& cam, bool came
     const unsigned work = std::max<unsigned>(std::max(n_a, n_b), use_prim ? n_frames * ((unsigned)sc.n_diag + 4) : 0u);
     const FrameTable none{};
     WF_LAUNCH(wf_frame_init, dim3(std::min<unsigned>((work + 255) / 256, 256u)), dim3(256), 0, stream, sc, cam,
-              d_prim_, use_prim ? 1u : 0u, (uint4*)d_cnt_, n_a, (uint4*)d_shard_, n_b, n_frames > 1 ? *batch : none,
+              d_prim_, use_prim ? 1u : 0u, (uint4*)d_cnt_, n_a, (uint4*)d_shard_, n_b, n_frames > 1 ? *job.batch : none,
               d_frames_, n_frames, fused ? d_gtab_ : (WfGenTab*)nullptr);
     WF_CHECK(hipGetLastError());
   }
-  const bool timed = ms_kernel != nullptr || (flags & WF_TIME) != 0;
+  const bool timed = (flags & WF_TIME) != 0;
   if (timed) WF_CHECK(hipEventRecord(ev0_, stream));
   if (profiling_) pframes_ += n_frames;  // class times are reported per frame
   prof_rays_[0] = prof_rays_[1] = prof_rays_[2] = 0;
@@ -512,21 +523,14 @@ hipError_t Wavefront::render(const DevScene& sc, const DevCamera& cam, bool came
   lr_.stream = stream;
   lr_.fused = fused;
   if (fused)
-    WF_CHECK(render_fast(sc, cam, camera_mode, d_in_rays, n0, frame_real, aa, max_depth, row_block, shard, n_shards,
-                         d_out, stream, sz, count, skip_shadow, tn, batch, n_frames));
+    WF_CHECK(render_fast(sc, job, n0, frame_real, stream, sz, skip_shadow, tn));
   else
-    WF_CHECK(render_exhaustive(sc, cam, camera_mode, d_in_rays, n0, aa, max_depth, row_block, shard, n_shards, d_out,
-                               stream, count, skip_shadow, tn, solo));
+    WF_CHECK(render_exhaustive(sc, job, stream, skip_shadow, tn, solo));
   if (timed) WF_CHECK(hipEventRecord(ev1_, stream));
   lr_.L = (unsigned)sc.n_lights; lr_.n0 = n0; lr_.max_depth = max_depth;
   lr_.counted = count; lr_.exact_disc = !bvh && !skip_shadow; lr_.bvh = bvh;
   lr_.n_diag = (unsigned long long)sc.n_diag; lr_.n_gen = (unsigned long long)sc.n_gen;
   lr_.n_planes = (unsigned long long)sc.n_planes; lr_.n_quads = (unsigned long long)sc.n_quads;
-  if (stats || ms_kernel) {
-    WF_CHECK(hipStreamSynchronize(stream));
-    if (ms_kernel) WF_CHECK(hipEventElapsedTime(ms_kernel, ev0_, ev1_));
-  }
-  if (stats) WF_CHECK(read_stats(stats));
   return hipSuccess;
 }
 
@@ -543,11 +547,12 @@ static unsigned long long gen_slots(unsigned long long n) {
 // ratios (WfSizing) or, when smaller, from the exact bound of the recursion
 // (every ray spawning `branch` children); a frame that outgrows them is
 // reported through the workspace's overflow record (take_overflow).
-hipError_t Wavefront::render_fast(const DevScene& sc, const DevCamera& cam, bool camera_mode, const double* d_in_rays,
-                                  unsigned n0, unsigned frame_real, unsigned aa, unsigned max_depth,
-                                  unsigned row_block, unsigned shard, unsigned n_shards, double* d_out,
-                                  hipStream_t stream, WfSizing& sz, bool count, bool skip_shadow, const WfTuning& tn,
-                                  const FrameTable* batch, unsigned n_frames) {
+hipError_t Wavefront::render_fast(const DevScene& sc, const WfJob& job, unsigned n0, unsigned frame_real,
+                                  hipStream_t stream, WfSizing& sz, bool skip_shadow, const WfTuning& tn) {
+  const DevCamera& cam = job.cam;
+  const bool camera_mode = job.camera_mode(), count = (job.flags & WF_COUNT) != 0;
+  const unsigned aa = job.aa, max_depth = job.max_depth, n_frames = job.n_frames;
+  double* const d_out = job.d_out;
   const bool averaged = aa > 1;
   const unsigned n_real = frame_real * n_frames;
   // ---- arena sizes
@@ -599,9 +604,9 @@ hipError_t Wavefront::render_fast(const DevScene& sc, const DevCamera& cam, bool
   }
   WF_CHECK(ea);
   if (!camera_mode)  // batch rays: n0 x 6 doubles -> generation 0's ray buffer
-    WF_CHECK(hipMemcpy2DAsync(rays_[0], sizeof(WfRay), d_in_rays, 6 * sizeof(double), 6 * sizeof(double), n0,
+    WF_CHECK(hipMemcpy2DAsync(rays_[0], sizeof(WfRay), job.d_in_rays, 6 * sizeof(double), 6 * sizeof(double), n0,
                               hipMemcpyDeviceToDevice, stream));
-  WfArgs a{};
+  WfArgs a = job_args(job, n0, frame_real);
   a.dev_sized = 1;
   a.colors_direct = averaged ? 0u : 1u;
   a.gtab = d_gtab_;
@@ -614,15 +619,6 @@ hipError_t Wavefront::render_fast(const DevScene& sc, const DevCamera& cam, bool
   a.par_cap = par_cap_;
   a.ray_cap = ray_cap_;
   a.hrec = d_rec_;
-  a.aa = aa;
-  a.rows = frame_real / aa / (cam.hsize ? cam.hsize : 1);
-  a.n_frames = n_frames; a.frame_rays = n0 / n_frames; a.frame_real = frame_real; a.frames = d_frames_;
-  a.cnt = d_cnt_;
-  a.prim = d_prim_;
-  a.max_depth = max_depth;
-  a.camera_mode = camera_mode ? 1u : 0u;
-  a.row_block = row_block; a.shard = shard; a.n_shards = n_shards;
-  a.blk_period = blk_period_; a.blk_mask = blk_mask_;
   a.skip_shadow = skip_shadow ? 1u : 0u;
   a.own_sphere = sc.obj_diag ? (unsigned)tn.own_sphere : 0u;
   a.spread = tn.spread ? 1u : 0u;
@@ -646,12 +642,11 @@ hipError_t Wavefront::render_fast(const DevScene& sc, const DevCamera& cam, bool
     WF_CHECK(pmark(stream, ccls, true));
     WF_CHECK(launch_fused(sc, cam, a, prim_launch, g == 0 ? n0 : kAnyRays, stream, count, tn));
     WF_CHECK(pmark(stream, ccls, false));
-    if (gen_ev_ && (int)g == gen_ev_g_) {
-      WF_CHECK(hipEventRecord(gen_ev_, stream));
+    if (job.gen_ev && (int)g == job.gen_ev_g) {
+      WF_CHECK(hipEventRecord(job.gen_ev, stream));
       gen_ev_done_ = true;
     }
   }
-  gen_ev_ = nullptr;
   // combine, deepest generation first (only the nodes with children; the last
   // generation has none). Generation 0's pass records the frame's counts.
   static int combine_grid = 0;
@@ -669,16 +664,11 @@ hipError_t Wavefront::render_fast(const DevScene& sc, const DevCamera& cam, bool
   if (averaged) {
     const unsigned n_pix = n_frames * (frame_real / aa);
     WF_CHECK(pmark(stream, WF_COMBINE, true));
-    WfArgs v{};
-    v.aa = aa; v.rows = frame_real / aa / cam.hsize;
-    v.n_frames = n_frames; v.frame_rays = n0 / n_frames; v.frame_real = frame_real; v.frames = d_frames_;
-    v.cnt = d_cnt_;
-    WF_LAUNCH(wf_average, dim3(occupancy_grid(wf_average, kWfBlock, 0, n_pix)), dim3(kWfBlock), 0, stream, v,
-              cam.hsize, colors_, n_pix, d_out);
+    WF_LAUNCH(wf_average, dim3(occupancy_grid(wf_average, kWfBlock, 0, n_pix)), dim3(kWfBlock), 0, stream,
+              job_args(job, n0, frame_real), cam.hsize, colors_, n_pix, d_out);
     WF_CHECK(hipGetLastError());
     WF_CHECK(pmark(stream, WF_COMBINE, false));
   }
-  (void)batch;
   lr_.last = max_depth;
   lr_.rays.clear();
   lr_.shadows.clear();
@@ -688,11 +678,12 @@ hipError_t Wavefront::render_fast(const DevScene& sc, const DevCamera& cam, bool
 // The exhaustive pipeline (the reference's every-shape loop, counted renders):
 // each generation's ray and shadow-ray counts are read back before the next
 // launch (synchronous); its buffers are per generation.
-hipError_t Wavefront::render_exhaustive(const DevScene& sc, const DevCamera& cam, bool camera_mode,
-                                        const double* d_in_rays, unsigned n0, unsigned aa, unsigned max_depth,
-                                        unsigned row_block, unsigned shard, unsigned n_shards, double* d_out,
-                                        hipStream_t stream, bool count, bool skip_shadow, const WfTuning& tn,
-                                        bool solo) {
+hipError_t Wavefront::render_exhaustive(const DevScene& sc, const WfJob& job, hipStream_t stream, bool skip_shadow,
+                                        const WfTuning& tn, bool solo) {
+  const DevCamera& cam = job.cam;
+  const bool camera_mode = job.camera_mode(), count = (job.flags & WF_COUNT) != 0;
+  const unsigned n0 = job.n0, aa = job.aa, max_depth = job.max_depth;
+  double* const d_out = job.d_out;
   const bool averaged = aa > 1;
   const unsigned L = (unsigned)sc.n_lights;
   std::vector<unsigned> rays(max_depth + 2, 0), shadows(max_depth + 2, 0);
@@ -700,7 +691,7 @@ hipError_t Wavefront::render_exhaustive(const DevScene& sc, const DevCamera& cam
   WF_CHECK(ensure_gen(0, n0, L, 0));
   if (!camera_mode) {
     // batch rays: n0 x 6 doubles -> WfRay queue of generation 0
-    WF_CHECK(hipMemcpy2DAsync(gens_[0].rays, sizeof(WfRay), d_in_rays, 6 * sizeof(double), 6 * sizeof(double), n0,
+    WF_CHECK(hipMemcpy2DAsync(gens_[0].rays, sizeof(WfRay), job.d_in_rays, 6 * sizeof(double), 6 * sizeof(double), n0,
                               hipMemcpyDeviceToDevice, stream));
   }
   const bool prim_lds = wf_lds_bytes(sc.n_diag, sc.n_gen, sc.n_planes, true) <= kWfLdsLimit;
@@ -735,18 +726,13 @@ hipError_t Wavefront::render_exhaustive(const DevScene& sc, const DevCamera& cam
     list_caps[g] = sh_cap;
     WF_CHECK(ensure_gen(g, g == 0 ? n : (size_t)kShards * caps[g], L, (size_t)kShards * sh_cap));
     WF_CHECK(ensure_gen(g + 1, (size_t)kShards * out_cap, L, 0));
-    WfArgs a{};
+    WfArgs a = job_args(job, n0, n0);
     WfGenBuf& B = gens_[g];
     a.rays = B.rays; a.hits = B.hits; a.nodes = B.nodes; a.shadow_nodes = B.shadow_nodes;
     a.geo = B.geo; a.surf = B.surf;
     a.colors = (g == 0 && !averaged) ? d_out : B.colors;
-    a.aa = aa;
-    a.rows = n0 / aa / (cam.hsize ? cam.hsize : 1);
-    a.n_frames = 1; a.frame_rays = n0; a.frame_real = n0;
     a.next_rays = gens_[g + 1].rays;
     a.child_colors = gens_[g + 1].colors;
-    a.cnt = d_cnt_;
-    a.prim = d_prim_;
     a.n = n;
     a.in_cnt = g == 0 ? nullptr : shard_cnt(g, 0);
     a.in_cap = caps[g];
@@ -754,10 +740,7 @@ hipError_t Wavefront::render_exhaustive(const DevScene& sc, const DevCamera& cam
     a.out_cap = out_cap;
     a.sh_cnt = shard_cnt(g, 1);
     a.sh_cap = sh_cap;
-    a.g = g; a.max_depth = max_depth;
-    a.camera_mode = camera_mode ? 1u : 0u;
-    a.row_block = row_block; a.shard = shard; a.n_shards = n_shards;
-    a.blk_period = blk_period_; a.blk_mask = blk_mask_;
+    a.g = g;
     a.skip_shadow = skip_shadow ? 1u : 0u;
     a.count = count ? 1u : 0u;
     // 1. closest hit
@@ -814,21 +797,15 @@ hipError_t Wavefront::render_exhaustive(const DevScene& sc, const DevCamera& cam
   }
   // 4. combine, deepest generation first
   for (int g = (int)last; g >= 0; --g) {
-    WfArgs a{};
+    WfArgs a = job_args(job, n0, n0);  // (wf_combine reads none of the workspace's records)
     WfGenBuf& B = gens_[g];
     a.rays = B.rays; a.nodes = B.nodes; a.surf = B.surf;
     a.colors = (g == 0 && !averaged) ? d_out : B.colors;
-    a.aa = aa;
-    a.rows = n0 / aa / (cam.hsize ? cam.hsize : 1);
-    a.n_frames = 1; a.frame_rays = n0; a.frame_real = n0;
     a.child_colors = gens_[g + 1].colors;
     a.n = rays[g];
     a.in_cnt = g == 0 ? nullptr : shard_cnt((unsigned)g, 0);
     a.in_cap = caps[g];
-    a.g = (unsigned)g; a.max_depth = max_depth;
-    a.camera_mode = camera_mode ? 1u : 0u;
-    a.row_block = row_block; a.shard = shard; a.n_shards = n_shards;
-    a.blk_period = blk_period_; a.blk_mask = blk_mask_;
+    a.g = (unsigned)g;
     if (a.n == 0) continue;
     WF_CHECK(pmark(stream, WF_COMBINE, true));
     WF_LAUNCH(wf_combine, dim3(occupancy_grid(wf_combine, kWfBlock, 0, a.n)), dim3(kWfBlock), 0, stream, sc, cam, a);
@@ -838,9 +815,8 @@ hipError_t Wavefront::render_exhaustive(const DevScene& sc, const DevCamera& cam
   if (averaged) {
     const unsigned n_pix = n0 / aa;
     WF_CHECK(pmark(stream, WF_COMBINE, true));
-    WfArgs a{};
-    a.aa = aa; a.rows = n0 / aa / cam.hsize;
-    a.n_frames = 1; a.frame_rays = n0; a.frame_real = n0;
+    WfArgs a = job_args(job, n0, n0);
+    a.cnt = nullptr;  // wf_average's overflow check is the fast path's: this pipeline runs it without counters
     WF_LAUNCH(wf_average, dim3(occupancy_grid(wf_average, kWfBlock, 0, n_pix)), dim3(kWfBlock), 0, stream, a,
               cam.hsize, gens_[0].colors, n_pix, d_out);
     WF_CHECK(hipGetLastError());

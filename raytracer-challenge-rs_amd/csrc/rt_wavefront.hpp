@@ -125,9 +125,9 @@ struct WfTuning {
 int wf_tuning_apply(WfTuning& t, const char* key, int value);
 
 // The fast path's launch over a global-memory scene image (lane 3 or 1) of
-// one generation: compiled into its own code object (rt_wavefront.hip built
-// with -DRT_WF_GLOBAL_TU). e0/e1: launch-carried profiling events, or null.
-struct DevCamera;
+// one generation: compiled into its own code object (rt_wavefront_glb.hip,
+// built without the scheduler's trackers). e0/e1: launch-carried profiling
+// events, or null.
 struct WfArgs;
 hipError_t wf_launch_global(int lane, bool quads, bool tally, bool cam_rays, const DevScene& sc, const DevCamera& cam,
                             const WfArgs& a, size_t dyn, unsigned n, hipStream_t stream, int block, hipEvent_t e0,
@@ -313,6 +313,64 @@ struct WfArgs {
   unsigned long long color_cap, par_cap, ray_cap;  // colour slots, parent records, ray slots per buffer
   WfHostRec* hrec;                  // device address of the workspace's host-mapped record
 };
+static_assert(sizeof(WfArgs) == 336, "WfArgs is the kernels' argument block: its layout is fixed");
+
+// What one pass of the pipeline renders: built by the entry points (through
+// the constructors below, then plain member assignment for what a site adds),
+// read by Wavefront::render and everything below it.
+struct WfJob {
+  DevCamera cam{};                    // camera mode (d_in_rays == nullptr): generation 0's rays come from it
+  const double* d_in_rays = nullptr;  // explicit rays instead (device, 6 doubles each)
+  unsigned n0 = 0;                    // root rays: pixels x aa of the shard (of one frame of a batch), or rays
+  unsigned aa = 1;                    // AA samples per pixel (averaged like Color::average)
+  unsigned max_depth = 0;
+  // the rows this render owns: shard `shard` of `n_shards` (blocks of row_block rows, block b
+  // on shard b mod n_shards), or with blk_period > 0 the blocks of a pattern (WfArgs::blk_mask)
+  unsigned row_block = 1, shard = 0, n_shards = 1;
+  unsigned blk_period = 0;
+  unsigned long long blk_mask = 0;
+  double* d_out = nullptr;            // n0 / aa * 3 doubles (device)
+  const FrameTable* batch = nullptr;  // n_frames > 1: every frame's camera and canvas (cam / d_out: frame 0's)
+  unsigned n_frames = 1;
+  unsigned flags = 0;                 // WF_EXHAUSTIVE | WF_COUNT | WF_TIME
+  // a fast-path render records gen_ev on its stream right after the launch of generation
+  // gen_ev_g (rt_render's bands: the next band may start while this one's deeper, smaller
+  // generations run); Wavefront::gen_event_recorded() tells whether it did
+  hipEvent_t gen_ev = nullptr;
+  int gen_ev_g = -1;
+
+  bool camera_mode() const { return d_in_rays == nullptr; }
+  static WfJob camera_shard(const DevCamera& cam, unsigned n0, unsigned aa, unsigned max_depth, double* d_out,
+                            unsigned row_block, unsigned shard = 0, unsigned n_shards = 1) {
+    WfJob j;
+    j.cam = cam; j.n0 = n0; j.aa = aa; j.max_depth = max_depth; j.d_out = d_out;
+    j.row_block = row_block; j.shard = shard; j.n_shards = n_shards;
+    return j;
+  }
+  static WfJob block_pattern(const DevCamera& cam, unsigned n0, unsigned aa, unsigned max_depth, double* d_out,
+                             unsigned row_block, unsigned period, unsigned long long mask) {
+    WfJob j = camera_shard(cam, n0, aa, max_depth, d_out, row_block);
+    j.blk_period = period; j.blk_mask = mask;
+    return j;
+  }
+  static WfJob ray_batch(const double* d_rays, unsigned n, unsigned max_depth, double* d_out) {
+    WfJob j;
+    j.d_in_rays = d_rays; j.n0 = n; j.max_depth = max_depth; j.d_out = d_out;
+    return j;
+  }
+};
+// The rules of a job, each stated once (the entry points report them through these too).
+inline bool wf_aa_valid(unsigned aa) { return aa != 0 && aa <= 16 && (aa & (aa - 1)) == 0; }
+// a pattern of `period` >= 1 blocks: a non-empty mask below 2^period
+inline bool wf_pattern_valid(unsigned period, unsigned long long mask) {
+  return period <= 64 && mask != 0 && (period == 64 || (mask >> period) == 0);
+}
+inline bool wf_job_valid(const WfJob& j) {
+  if (j.max_depth + 2 > (unsigned)kMaxGen) return false;
+  if (j.blk_period && !wf_pattern_valid(j.blk_period, j.blk_mask)) return false;  // (period 0: the mask is not read)
+  if (!wf_aa_valid(j.aa) || (!j.camera_mode() && j.aa != 1) || j.n0 % j.aa != 0) return false;
+  return j.n_frames != 0 && j.n_frames <= kMaxFrames && (j.n_frames == 1 || j.batch != nullptr);
+}
 
 // Per-kernel-class timing of the last frame (profiling mode only).
 enum WfClass { WF_PRIMARY = 0, WF_CLOSEST = 1, WF_SHADOW = 2, WF_PREP = 3, WF_COMBINE = 4, WF_NCLASS = 5 };
@@ -341,26 +399,17 @@ class Wavefront {
   // Per-class times averaged over the frames rendered since profiling was
   // enabled; rays / disc counts of the last frame (synchronises).
   hipError_t last_profile(WfProfile* out);
-  // Render n0 root rays (camera pixels x `aa` samples of a shard, or explicit
-  // rays) into `out` (n0/aa*3 doubles, device; AA samples are averaged like
-  // Color::average). The fast path (BVH) is fully asynchronous: every
-  // generation sizes itself on the device (WfGenTab); `sz` sizes the arenas.
-  // The exhaustive pipeline (WF_EXHAUSTIVE or a scene without hierarchies)
-  // reads each generation's count back (synchronous). stats (host) may be
-  // null. `solo`: no other workspace renders concurrently (then the
-  // exhaustive shadow traces take the side stream).
-  // `flags`: WF_EXHAUSTIVE runs the reference's every-shape loop (exact
-  // sphere_disc_ge0); WF_COUNT counts the reference's rays of this render
-  // (read later by read_stats). A non-null `stats` implies WF_COUNT and
-  // synchronises to fill it.
-  // `blk_period` / `blk_mask`: a block-pattern render (WfArgs::blk_mask) instead of
-  // shard `shard` of `n_shards` (blk_period 0).
-  hipError_t render(const DevScene& sc, const DevCamera& cam, bool camera_mode, const double* d_in_rays,
-                    unsigned n0, unsigned aa, unsigned max_depth, unsigned row_block, unsigned shard,
-                    unsigned n_shards, double* d_out, hipStream_t stream, WfSizing& sz, DevStats* stats,
-                    float* ms_kernel, const WfTuning& tn, bool solo = true, unsigned flags = 0,
-                    const FrameTable* batch = nullptr, unsigned n_frames = 1, unsigned blk_period = 0,
-                    unsigned long long blk_mask = 0);
+  // Render the job's root rays into its d_out. The fast path (BVH) is fully
+  // asynchronous: every generation sizes itself on the device (WfGenTab); `sz`
+  // sizes the arenas. The exhaustive pipeline (WF_EXHAUSTIVE or a scene without
+  // hierarchies) reads each generation's count back (synchronous). `solo`: no
+  // other workspace renders concurrently (then the exhaustive shadow traces
+  // take the side stream). WF_COUNT counts the reference's rays of this render
+  // (read later by read_stats), WF_TIME brackets it with events (kernel_ms);
+  // neither synchronises. hipErrorInvalidValue: not wf_job_valid, or a batch
+  // that cannot run as one (only uncounted camera renders on the fast path can).
+  hipError_t render(const DevScene& sc, const WfJob& job, hipStream_t stream, WfSizing& sz, const WfTuning& tn,
+                    bool solo);
   // The counters of the last render (rendered with WF_COUNT); synchronises its stream.
   hipError_t read_stats(DevStats* out);
   // Rays of each generation of the last render (synchronises its stream).
@@ -377,23 +426,18 @@ class Wavefront {
   // The learned sizes from this workspace's last recorded frame (non-blocking:
   // the record of a frame still in flight may be stale).
   void learn(WfSizing& sz) const;
-  // The next fast-path render records `ev` on its stream right after the launch
-  // of generation g (rt_render's bands: the next band may start while this one's
-  // deeper, smaller generations run); gen_event_recorded() tells whether it did
-  // (a render with fewer generations, or an exhaustive one, does not).
-  void set_gen_event(hipEvent_t ev, int g) { gen_ev_ = ev; gen_ev_g_ = g; gen_ev_done_ = false; }
+  // The last render recorded its job's gen_ev (a render with fewer generations,
+  // or an exhaustive one, does not).
   bool gen_event_recorded() const { return gen_ev_done_; }
 
  private:
-  hipError_t render_fast(const DevScene& sc, const DevCamera& cam, bool camera_mode, const double* d_in_rays,
-                         unsigned n0, unsigned frame_real, unsigned aa, unsigned max_depth, unsigned row_block,
-                         unsigned shard, unsigned n_shards, double* d_out, hipStream_t stream, WfSizing& sz,
-                         bool count, bool skip_shadow, const WfTuning& tn, const FrameTable* batch,
-                         unsigned n_frames);
-  hipError_t render_exhaustive(const DevScene& sc, const DevCamera& cam, bool camera_mode, const double* d_in_rays,
-                               unsigned n0, unsigned aa, unsigned max_depth, unsigned row_block, unsigned shard,
-                               unsigned n_shards, double* d_out, hipStream_t stream, bool count, bool skip_shadow,
+  // n0: the pass's generation-0 slots (a batch: n_frames x the padded frame), frame_real: one frame's root rays
+  hipError_t render_fast(const DevScene& sc, const WfJob& job, unsigned n0, unsigned frame_real, hipStream_t stream,
+                         WfSizing& sz, bool skip_shadow, const WfTuning& tn);
+  hipError_t render_exhaustive(const DevScene& sc, const WfJob& job, hipStream_t stream, bool skip_shadow,
                                const WfTuning& tn, bool solo);
+  // the fields every launch of a pass shares (the job's, and this workspace's counters and records)
+  WfArgs job_args(const WfJob& job, unsigned n0, unsigned frame_real) const;
   hipError_t ensure_gen(size_t g, size_t slots, size_t n_lights, size_t list_slots);
   hipError_t ensure_misc(size_t n_diag, unsigned n_frames = 1);
   hipError_t ensure_arenas(unsigned long long colors, unsigned long long parents, unsigned long long rays,
@@ -434,11 +478,7 @@ class Wavefront {
   // generation counts of the last render (fast path: from the host-mapped record; synchronises)
   hipError_t last_counts(std::vector<unsigned>& rays);
   bool last_bvh_ = false, last_fused_ = false;
-  hipEvent_t gen_ev_ = nullptr;  // set_gen_event: recorded on the stream after generation gen_ev_g_'s launch
-  int gen_ev_g_ = -1;
-  bool gen_ev_done_ = false;
-  unsigned blk_period_ = 0;  // the current render's block pattern (render())
-  unsigned long long blk_mask_ = 0;
+  bool gen_ev_done_ = false;  // gen_event_recorded()
   bool profiling_ = false;
   int pmask_ = (1 << WF_NCLASS) - 1;
   std::vector<hipEvent_t> pev_;        // event pool (pairs)

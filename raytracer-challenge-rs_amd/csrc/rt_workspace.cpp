@@ -1,7 +1,8 @@
 // rt_workspace.cpp — one render through the scene's workspace pool
 // (run_render: a wavefront workspace per stream, overflow detection and
-// re-render), the overflow check of earlier asynchronous frames, the
-// device-to-host copy into caller memory, and the counters' conversion.
+// re-render; settle: the read-back of a workspace its caller kept pinned),
+// the overflow check of earlier asynchronous frames, the device-to-host copy
+// into caller memory, and the counters' conversion.
 #include "rt_api_internal.hpp"
 
 namespace rtapi {
@@ -112,68 +113,55 @@ int check_faults(rt_scene* s) {
   return RT_OK;
 }
 
-// Launch one render (camera shard or ray batch) on `stream` through the
-// wavefront pipeline. `n_tasks` root rays = pixels x aa (camera) or rays
-// (batch). `stats_out`, when given, receives the exact counters and
-// `ms_out` the kernel time. `sync`: the caller waits for this render anyway
-// (a host canvas, the counters): the call waits for it, and a frame that
-// overflowed its queue arenas is rendered again, with the arenas grown,
+// Launch one render (the job: a camera shard, a block pattern, a batch of
+// frames or a ray batch) on `stream` through the wavefront pipeline, on the
+// stream's workspace of the scene's pool. How it runs is the RenderCall:
+// `sync` (implied by `stats` and `time`): the caller waits for this render
+// anyway (a host canvas, the counters): the call waits for it, and a frame
+// that overflowed its queue arenas is rendered again, with the arenas grown,
 // until it fits (every synchronous entry point returns a complete frame).
 // Asynchronous renders report an overflow later (check_faults). With `lk`
-// (the scene's lock, held on entry and on return) the waits run unlocked;
-// the workspace stays pinned to this call meanwhile. `used` receives the
-// workspace; with `keep_pin` it stays pinned after the return (the caller
-// reads it back and unpins it, under the scene's lock). `count`: the render
-// counts the reference's rays (read_stats) without synchronising.
-int run_render(rt_scene* s, const DevCamera& cam, const double* d_rays, uint32_t n_tasks, uint32_t aa,
-               uint32_t max_depth, uint32_t row_block, uint32_t shard, uint32_t n_shards, double* d_out,
-               hipStream_t stream, DevStats* stats_out, float* ms_out, uint32_t flags, rt_scene::WfSlot** used,
-               const FrameTable* batch, unsigned n_frames, bool sync, std::unique_lock<std::mutex>* lk, bool count,
-               bool keep_pin, uint32_t blk_period, uint64_t blk_mask, hipEvent_t gen_ev, int gen_ev_g,
-               bool* gen_ev_recorded, WfSizing* sizing) {
-  WfSizing& sz = sizing ? *sizing : s->sizing;
-  if (max_depth > (uint32_t)kMaxDepth)
+// (the scene's lock, held on entry and on return) the waits run unlocked; the
+// workspace stays pinned to this call meanwhile. With `keep_pin` it stays
+// pinned after the return, in the caller's guard, for the caller to wait on
+// the render and settle() it. `res` receives what the call asked for.
+int run_render(rt_scene* s, const WfJob& job_in, hipStream_t stream, const RenderCall& call, RenderResult* res) {
+  WfSizing& sz = call.sizing ? *call.sizing : s->sizing;
+  if (res) *res = RenderResult{};
+  DevStats* stats_out = call.stats && res ? &res->stats : nullptr;
+  float* ms_out = call.time && res ? &res->ms : nullptr;
+  if (job_in.max_depth > (uint32_t)kMaxDepth)
     return fail(RT_ERR_INVALID_ARGUMENT, "max_depth > " + std::to_string(kMaxDepth));
-  if (!valid_aa(aa)) return fail(RT_ERR_INVALID_ARGUMENT, "aa_samples must be 1, 2, 4, 8 or 16");
-  if (flags & ~(uint32_t)RT_RENDER_EXHAUSTIVE) return fail(RT_ERR_INVALID_ARGUMENT, "unknown render flags");
+  if (!valid_aa(job_in.aa)) return fail(RT_ERR_INVALID_ARGUMENT, "aa_samples must be 1, 2, 4, 8 or 16");
+  if (call.flags & ~(uint32_t)RT_RENDER_EXHAUSTIVE) return fail(RT_ERR_INVALID_ARGUMENT, "unknown render flags");
   int rc = check_faults(s);
   if (rc != RT_OK) return rc;
-  if (n_tasks == 0) {
-    if (stats_out) *stats_out = DevStats{};
-    if (ms_out) *ms_out = 0.f;
-    if (used) *used = nullptr;
-    return RT_OK;
-  }
+  if (job_in.n0 == 0) return RT_OK;
   rt_scene::WfSlot* w = nullptr;
   hipError_t e = s->acquire(stream, &w);
   if (e != hipSuccess) return fail(RT_ERR_HIP, std::string("wavefront render: ") + hipGetErrorString(e));
-  const unsigned wf_flags = ((flags & RT_RENDER_EXHAUSTIVE) ? WF_EXHAUSTIVE : 0u) |
-                            ((count || stats_out) ? WF_COUNT : 0u) | (ms_out ? WF_TIME : 0u);
-  sync = sync || stats_out || ms_out;
-  struct Pin {  // the workspace is this call's until it returns (keep_pin: until the caller unpins it)
+  WfJob job = job_in;
+  job.flags |= ((call.flags & RT_RENDER_EXHAUSTIVE) ? WF_EXHAUSTIVE : 0u) |
+               ((call.count || stats_out) ? WF_COUNT : 0u) | (ms_out ? WF_TIME : 0u);
+  const bool sync = call.sync || stats_out || ms_out;
+  struct Pin {  // the workspace is this call's until it returns (keep_pin: until the caller's guard lets go)
     rt_scene::WfSlot* w;
     bool on;
     ~Pin() {
       if (on) --w->pins;
     }
-  } pin{w, sync && !keep_pin};
-  if (sync || keep_pin) ++w->pins;
-  if (keep_pin && used) *used = w;
+  } pin{w, sync && !call.keep_pin};
+  if (sync || call.keep_pin) ++w->pins;
+  if (call.keep_pin) call.keep_pin->w = w;
   for (int attempt = 0;; ++attempt) {
-    if (gen_ev) w->wf->set_gen_event(gen_ev, gen_ev_g);
-    e = w->wf->render(s->dev, cam, d_rays == nullptr, d_rays, n_tasks, aa, max_depth, row_block, shard, n_shards,
-                      d_out, stream, sz, nullptr, nullptr, s->tune, s->wfs.size() == 1, wf_flags, batch,
-                      n_frames, blk_period, blk_mask);
-    if (gen_ev) {
-      if (gen_ev_recorded) *gen_ev_recorded = w->wf->gen_event_recorded();
-      w->wf->set_gen_event(nullptr, -1);
-    }
+    e = w->wf->render(s->dev, job, stream, sz, s->tune, s->wfs.size() == 1);
+    if (job.gen_ev && res) res->gen_ev_recorded = w->wf->gen_event_recorded();
     if (e == hipSuccess) e = hipEventRecord(w->done, stream);
     if (e != hipSuccess) return fail(RT_ERR_HIP, std::string("wavefront render: ") + hipGetErrorString(e));
     if (!sync) break;
-    if (lk) lk->unlock();
+    if (call.lk) call.lk->unlock();
     e = hipStreamSynchronize(stream);
-    if (lk) lk->lock();
+    if (call.lk) call.lk->lock();
     if (e != hipSuccess) return fail(RT_ERR_HIP, std::string("wavefront render: ") + hipGetErrorString(e));
     w->wf->learn(sz);
     bool over = false;
@@ -184,7 +172,17 @@ int run_render(rt_scene* s, const DevCamera& cam, const double* d_rays, uint32_t
   }
   if (stats_out) RT_HIP(w->wf->read_stats(stats_out));
   if (ms_out) RT_HIP(w->wf->kernel_ms(ms_out));
-  if (used) *used = w;
+  return RT_OK;
+}
+
+int settle(PinGuard& pin, WfSizing& sz, bool* over) {
+  *over = false;
+  if (!pin.w) return RT_OK;
+  pin.w->wf->learn(sz);
+  const hipError_t e = pin.w->wf->take_overflow(over);
+  --pin.w->pins;
+  pin.w = nullptr;
+  if (e != hipSuccess) return fail(RT_ERR_HIP, std::string("wavefront arenas: ") + hipGetErrorString(e));
   return RT_OK;
 }
 
