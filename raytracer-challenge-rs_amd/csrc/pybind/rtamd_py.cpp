@@ -83,7 +83,7 @@ extern "C" int rtamd_nccl_comm_init(int nranks, const unsigned char* id, size_t 
 extern "C" int rtamd_nccl_comm_abort(void* comm);
 extern "C" int rtamd_nccl_gather_f64(const double* send, double* recv, size_t count, int root, void* comm, void* stream);
 extern "C" int rtamd_nccl_comm_destroy(void* comm);
-extern "C" int rtamd_wf_profile(const rt_scene* s, int enable, double out[38]);
+extern "C" int rtamd_wf_profile(const rt_scene* s, int enable, double out[40]);
 extern "C" int rtamd_wf_gen_counts(const rt_scene* s, unsigned* out, int max);
 extern "C" int rtamd_scene_tuning_set(const rt_scene* s, const char* key, int value);
 extern "C" int rtamd_render_shard_host(const rt_scene* scene, const rt_camera_desc* camera, uint32_t max_depth,
@@ -628,7 +628,7 @@ PYBIND11_MODULE(_rtamd, m) {
     return l;
   }, py::arg("world"));
   m.def("_wf_profile", [](const World& w, int enable, bool read) {
-    double o[38] = {0};
+    double o[40] = {0};
     check(rtamd_wf_profile(w.scene(), enable, read ? o : nullptr), "wf_profile");
     py::dict d;
     if (read) {
@@ -649,6 +649,7 @@ PYBIND11_MODULE(_rtamd, m) {
       d["shadow_rays_in"] = shr; d["shadow_tests_in"] = sht; d["fused"] = (bool)o[33];
       d["n_bvh_wide"] = (int)o[34]; d["wide_stack"] = (int)o[35];
       d["n_lbvh_nodes"] = (int)o[36]; d["n_line_culled"] = (int)o[37];
+      d["lane_primary"] = (int)o[38]; d["lane_secondary"] = (int)o[39];
     }
     return d;
   }, py::arg("world"), py::arg("enable") = -1, py::arg("read") = true);

@@ -56,13 +56,15 @@ extern "C" {
 const char* rt_last_error(void) { return g_err.c_str(); }
 
 // Development/benchmark hook (not in the public ABI): per-kernel-class timing
-// of the wavefront pipeline. enable: 1 = on, 0 = off, -1 = just read. out[16]:
+// of the wavefront pipeline. enable: 1 = on, 0 = off, -1 = just read. out[40]:
 // ms[5] (primary, closest, shadow, prep, combine), rays[3], disc[3],
 // n_diag, n_gen, n_planes, n_lights, n_quads, tests[3], boxes[3], bvh,
 // n_bvh_nodes, bvh_depth, n_obvh_nodes, n_other_culled, lb_res, lb_items, sh_rays[2], sh_tests[2]
 // (shadow rays / sphere tests inside the fused primary / secondary launches), fused,
-// n_bvh_wide, wide_stack, n_lbvh_nodes, n_line_culled.
-int rtamd_wf_profile(const rt_scene* cs, int enable, double out[38]) {
+// n_bvh_wide, wide_stack, n_lbvh_nodes, n_line_culled, lane_primary, lane_secondary (the scene
+// images of the last render's fused launches, rt_wf_plan.hpp: generation 0's and the last deeper
+// generation's; -1 when the render was not fused or had no such launch).
+int rtamd_wf_profile(const rt_scene* cs, int enable, double out[40]) {
   if (!cs) return fail(RT_ERR_INVALID_ARGUMENT, "null scene");
   rt_scene* s = const_cast<rt_scene*>(cs);
   std::lock_guard<std::mutex> lk(s->mu);
@@ -109,6 +111,8 @@ int rtamd_wf_profile(const rt_scene* cs, int enable, double out[38]) {
     out[35] = s->dev.bvhw ? s->dev.bvhw_stack : 0;
     out[36] = s->dev.n_lbvh;
     out[37] = s->dev.n_lrec;
+    out[38] = s->last_wf ? p.lane_primary : -1;
+    out[39] = s->last_wf ? p.lane_secondary : -1;
   }
   return RT_OK;
 }

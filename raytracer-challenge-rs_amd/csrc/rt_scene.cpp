@@ -3,6 +3,7 @@
 // records in the reference's object order, the exact-culling hierarchies
 // (rt_bvh.cpp), the light buffer, and one upload to the scene's device.
 #include "rt_api_internal.hpp"
+#include "rt_wf_plan.hpp"
 
 using namespace rtapi;
 
@@ -174,9 +175,7 @@ int rt_scene_create_groups(const rt_shape_desc* shapes, size_t n_shapes, const i
   if (g_bvh_leaf == 0 && !bvh.empty()) {
     // a scene whose pair image (stack, nodes, sphere records) does not fit in
     // LDS is traversed from global memory, where single-sphere leaves win
-    const size_t image = (size_t)(bvh_depth + 1) * kFusedBlockThreads * 4 + bvh.size() * sizeof(BvhNode) +
-                         diag.size() * sizeof(SphereDiag);
-    if (image > kFusedLdsLimit) bvh = build_sphere_bvh(diag, 1, &bvh_depth, g_bvh_ct / 100.0);
+    if (pair_image_leaf_estimate(bvh_depth, bvh.size(), diag.size()) > kFusedLdsLimit) bvh = build_sphere_bvh(diag, 1, &bvh_depth, g_bvh_ct / 100.0);
   }
   const std::vector<BvhPair> bvh_pair = pair_layout(bvh);
   int wide_stack = 0;

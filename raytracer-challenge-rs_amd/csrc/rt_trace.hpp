@@ -10,12 +10,11 @@
 
 #include "rt_device.hpp"
 #include "rt_wavefront.hpp"
+#include "rt_wf_plan.hpp"
 
 #pragma clang fp contract(off)
 
 namespace rtamd {
-
-constexpr int kTraceBlock = 1024;  // trace kernels: 16 waves, one LDS image per block
 
 __device__ __forceinline__ unsigned lane_id() { return __lane_id(); }
 
@@ -746,37 +745,6 @@ __device__ __forceinline__ void count_hier_gates(const DevScene& sc, V3 o, V3 d,
   }
 }
 
-__host__ __device__ inline size_t lane_stack_bytes(int depth) { return (size_t)(depth > 0 ? depth : 1) * kTraceBlock * 4; }
-__host__ __device__ inline size_t sph_lds_bytes(const DevScene& sc) { return (size_t)sc.n_diag * sizeof(SphereDiag); }
-// the pair image's sphere records: 48 B each, then the metas (Sph48)
-__host__ __device__ inline size_t sph48_lds_bytes(const DevScene& sc) {
-  return (size_t)sc.n_diag * 48 + (((size_t)sc.n_diag * 4 + 15) & ~(size_t)15);
-}
-// The light buffer's distances in LDS as binary16 lower bounds of the binary32
-// ones (2 B each): a stored value never exceeds the true distance, so a walk
-// that stops at the first stored distance beyond the origin stops no earlier
-// than the exact walk would (lb_walk).
-__host__ __device__ inline size_t delta_lds_bytes(const DevScene& sc) {
-  return sc.lb_cells ? (((size_t)sc.n_lights * sc.n_diag * sizeof(_Float16) + 15) & ~(size_t)15) : 0;
-}
-// LANE 14: [16-bit stack (bvh_depth + 1 with the sentinel) x kTraceBlock][pair nodes][Sph48 records]
-// (no pair image without the scene's 16-bit pair codes: rt_bvh.cpp pair_layout)
-__host__ __device__ inline size_t pair_lds_bytes(const DevScene& sc) {
-  if (!sc.bvh_pair) return (size_t)1 << 40;
-  return ((lane_stack_bytes(sc.bvh_depth + 1) / 2 + 15) & ~(size_t)15) + (size_t)sc.n_bvh * sizeof(BvhNode) +
-         sph48_lds_bytes(sc);
-}
-// LANE 4: the 16-bit stack (sc.bvhw_stack entries) x kTraceBlock, before the distances and the treelet
-__host__ __device__ inline size_t wide_stack_bytes(const DevScene& sc) {
-  return ((size_t)(sc.bvhw_stack > 0 ? sc.bvhw_stack : 1) * kTraceBlock * 2 + 15) & ~(size_t)15;
-}
-// LANE 15: [16-bit stack][every wide node][Sph48 records]
-__host__ __device__ inline size_t wide_lds_bytes(const DevScene& sc) {
-  if (!sc.bvhw) return (size_t)1 << 40;
-  return wide_stack_bytes(sc) + (size_t)sc.n_bvhw * sizeof(BvhWide) + sph48_lds_bytes(sc);
-}
-constexpr unsigned kLdsSpheres = 1u, kLdsDeltas = 2u;  // lane_scene's lds_flags (LANE 0: records; all: distances)
-
 struct LaneScene {
   const unsigned char* nodes;  // pair layout in LDS (14) or BvhNode[] in global memory
   const SphereDiag* sd;        // sphere records (LDS or global; not LANE 14)
@@ -791,6 +759,10 @@ struct LaneScene {
   const BvhWide* wtop;         // 15: the LDS copy of the wide nodes
   const BvhWide16* wtop16;     // 4: the LDS copy of the first n_top binary16 wide nodes
 };
+// Stages the block's LDS image. The regions it walks over are those of
+// lane_lds_layout (rt_wf_plan.hpp), by which the host sizes the launch's dynamic
+// LDS; tests/cpp/plan_check.cpp holds this walk and that layout together. (Taking
+// the offsets from the layout here moves instructions in every image's kernel.)
 template <int LANE>
 __device__ __forceinline__ LaneScene lane_scene(const DevScene& sc, unsigned lds_flags, unsigned n_top, int* static_stack,
                                                 unsigned char* dyn) {

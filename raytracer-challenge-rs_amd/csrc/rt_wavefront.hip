@@ -14,9 +14,7 @@
 // loop, launches). Device code: rt_wf_device.hpp (trace and fused kernels),
 // rt_wf_combine.hip (frame init, combine, average), rt_wavefront_glb.hip (the
 // launches over the global-memory images, their own code object).
-#include "rt_wf_device.hpp"
-
-#include <hip/hip_ext.h>
+#include "rt_wf_launch.hpp"
 
 #include <algorithm>
 #include <cstring>
@@ -139,6 +137,8 @@ hipError_t Wavefront::last_profile(WfProfile* out) {
   if (last_fused_) out->rays[WF_SHADOW] = out->sh_rays[0] + out->sh_rays[1];  // traced inside the fused launches
   out->bvh = last_bvh_ ? 1 : 0;
   out->fused = last_fused_ ? 1 : 0;
+  out->lane_primary = plan_primary_.lane;
+  out->lane_secondary = plan_secondary_.lane;
   return hipSuccess;
 }
 
@@ -284,21 +284,6 @@ hipError_t Wavefront::ensure_misc(size_t n_diag, unsigned n_frames) {
   return hipSuccess;
 }
 
-template <typename K>
-static int occupancy_grid(K kern, int block, size_t lds, unsigned n) {
-  int dev = 0, n_cu = 0, per_cu = 0;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
-  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, block, lds) != hipSuccess || per_cu < 1) per_cu = 1;
-  long long want = ((long long)n + block - 1) / block;
-  long long cap = (long long)n_cu * per_cu;
-  long long g = std::min(want, cap);
-  return (int)std::max(g, 1LL);
-}
-
-static constexpr size_t kWfLdsLimit = kFusedLdsLimit;
-static_assert(kFusedBlockThreads == kTraceBlock, "rt_api.cpp sizes the pair image with kFusedBlockThreads");
-
 // Threads per block of a trace launch over n rays. A trace block holds one CU
 // (its LDS image), so a launch of fewer than (CUs x kTraceBlock) rays would
 // leave CUs idle with full-size blocks: such launches spread their rays over
@@ -331,12 +316,11 @@ static int trace_block(unsigned n, int adaptive) {
     }                                                                                                  \
   } while (0)
 
-template <typename K>
-static hipError_t launch_lds(K kern, size_t lds, unsigned n, hipStream_t stream, const DevScene& sc,
-                             const DevCamera& cam, const WfArgs& a, int block) {
-  if (lds > 0) WF_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  WF_LAUNCH(kern, dim3(occupancy_grid(kern, block, lds, n)), dim3(block), lds, stream, sc, cam, a);
-  return hipGetLastError();
+// A launch through wf_launch (rt_wf_launch.hpp), with the timed class's events.
+template <typename K, typename... Args>
+static hipError_t launch_timed(K kern, int block, size_t dyn, unsigned n, hipStream_t stream, const Args&... args) {
+  if (t_ev_start) ++t_ev_used;
+  return wf_launch(kern, block, dyn, n, stream, t_ev_start, t_ev_stop, args...);
 }
 
 // ---- the exhaustive pipeline (counted launches: the reference's every-shape loop)
@@ -345,118 +329,55 @@ static hipError_t launch_closest_exh(const DevScene& sc, const DevCamera& cam, c
                                      bool lds_ok, unsigned n, hipStream_t stream, const WfTuning& tn) {
   const int tb = trace_block(n, tn.adaptive_block);
   if (primary)
-    return launch_lds(wf_trace_closest<true, true, QUADS, 8>, wf_lds_bytes(sc.n_diag, sc.n_gen, sc.n_planes, true),
-                      n, stream, sc, cam, a, tb);
+    return launch_timed(wf_trace_closest<true, true, QUADS, 8>, tb, wf_lds_bytes(sc.n_diag, sc.n_gen, sc.n_planes, true),
+                        n, stream, sc, cam, a);
   if (lds_ok)
-    return launch_lds(wf_trace_closest<true, false, QUADS, 8>, wf_lds_bytes(sc.n_diag, sc.n_gen, sc.n_planes, false),
-                      n, stream, sc, cam, a, tb);
-  return launch_lds(wf_trace_closest<false, false, QUADS, 8>, 0, n, stream, sc, cam, a, tb);
+    return launch_timed(wf_trace_closest<true, false, QUADS, 8>, tb,
+                        wf_lds_bytes(sc.n_diag, sc.n_gen, sc.n_planes, false), n, stream, sc, cam, a);
+  return launch_timed(wf_trace_closest<false, false, QUADS, 8>, tb, 0, n, stream, sc, cam, a);
 }
 template <bool QUADS>
 static hipError_t launch_shadow_exh(const DevScene& sc, const WfArgs& a, bool lds_ok, hipStream_t stream,
                                     const WfTuning& tn) {
   const int tb = trace_block(a.n_shadow, tn.adaptive_block);
-  if (lds_ok) {
-    const size_t lds = wf_lds_bytes(sc.n_diag, sc.n_gen, sc.n_planes, false);
-    auto k = wf_trace_shadow<true, QUADS, 8>;
-    WF_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    WF_LAUNCH(k, dim3(occupancy_grid(k, tb, lds, a.n_shadow)), dim3(tb), lds, stream, sc, a);
-  } else {
-    auto k = wf_trace_shadow<false, QUADS, 8>;
-    WF_LAUNCH(k, dim3(occupancy_grid(k, tb, 0, a.n_shadow)), dim3(tb), 0, stream, sc, a);
-  }
-  return hipGetLastError();
+  if (lds_ok)
+    return launch_timed(wf_trace_shadow<true, QUADS, 8>, tb, wf_lds_bytes(sc.n_diag, sc.n_gen, sc.n_planes, false),
+                        a.n_shadow, stream, sc, a);
+  return launch_timed(wf_trace_shadow<false, QUADS, 8>, tb, 0, a.n_shadow, stream, sc, a);
 }
 
-// the global-memory images' launches live in their own code object (rt_wavefront_glb.o)
-static hipError_t launch_global(int lane, bool quads, bool tally, bool cam_rays, const DevScene& sc,
-                                const DevCamera& cam, const WfArgs& a, size_t dyn, unsigned n, hipStream_t stream,
-                                int block) {
-  const hipError_t e =
-      wf_launch_global(lane, quads, tally, cam_rays, sc, cam, a, dyn, n, stream, block, t_ev_start, t_ev_stop);
-  if (t_ev_start) ++t_ev_used;
-  return e;
-}
-
-// ---- the fast path: one fused launch per generation (image choice: see lane_scene)
+// ---- the fast path: one fused launch per generation over the image wf_plan_image chooses
+// (rt_wf_plan.hpp); `ran` receives the plan. The global-memory images' launches live in their
+// own code object (rt_wavefront_glb.o).
 template <bool QUADS, bool TALLY>
 static hipError_t launch_fused_q(const DevScene& sc, const DevCamera& cam, WfArgs a, bool primary, unsigned n,
-                                 hipStream_t stream, const WfTuning& tn) {
+                                 hipStream_t stream, const WfTuning& tn, WfImagePlan* ran) {
   // (spread: the whole grid, whatever n; the kernel deals the chunks over every block)
   if (a.spread && !tn.adaptive_block) n = 1u << 30;
   const int tb = trace_block(n, tn.adaptive_block);
-  const size_t dl = a.use_lb ? delta_lds_bytes(sc) : 0;
-  size_t dyn = 0;
-  a.lds_flags = 0;
-  // primary rays: the wave traversal, or with prim_lane the per-lane walk of the pair image or of
-  // the four-wide hierarchy (the launches below, reading camera rays)
-  const bool wide_ok = tn.image != 1 && tn.wide && sc.bvhw16 && wide_stack_bytes(sc) <= kWfLdsLimit / 2;
-  // prim_lane 1 (default): any per-lane image (C3 primary class 0.128 -> 0.125 ms/frame with the LDS
-  // four-wide image; C5's global image: 2.06 -> 2.16 ms with binary32 nodes in round 4, 2.17 -> 2.01
-  // ms with the binary16 ones, round 6); 2: the LDS images only
-  const bool wide_lds = sc.bvhw && tn.lds_wide && wide_lds_bytes(sc) + dl <= kWfLdsLimit;
-  const bool lds_img = tn.image == 0 && (pair_lds_bytes(sc) <= kWfLdsLimit || wide_lds);
-  const bool lane_prim = tn.prim_lane == 1 ? (lds_img || wide_ok) : tn.prim_lane == 2 ? lds_img : false;
-  if (primary && !lane_prim) {
-    const size_t room = kWfLdsLimit - (size_t)(kTraceBlock / 64) * (kBvhMaxDepth + 4) * 4;
-    if (sph_lds_bytes(sc) <= room) { a.lds_flags |= kLdsSpheres; dyn += sph_lds_bytes(sc); }
-    if (dl && dyn + dl <= room) { a.lds_flags |= kLdsDeltas; dyn += dl; }
-    return launch_lds(wf_trace_fused<true, QUADS, 0, TALLY>, dyn, n, stream, sc, cam, a, tb);
-  }
+  const WfImagePlan plan = *ran = wf_plan_image(sc, tn, primary, a.use_lb != 0);
+  a.lds_flags = plan.lds_flags;
+  a.n_top = plan.n_top;
   const bool cam_rays = a.g == 0 && a.camera_mode;  // only generation 0 of a camera render reads camera rays
-  if (tn.image == 0 && wide_lds) {
-    // the four-wide hierarchy and the 48-B sphere records in LDS, with the light buffer's distances
-    dyn = wide_lds_bytes(sc);
-    if (dl) { a.lds_flags |= kLdsDeltas; dyn += dl; }
-    return cam_rays ? launch_lds(wf_trace_fused<false, QUADS, 15, TALLY, true>, dyn, n, stream, sc, cam, a, tb)
-                    : launch_lds(wf_trace_fused<false, QUADS, 15, TALLY, false>, dyn, n, stream, sc, cam, a, tb);
+#define RT_LDS(P, L, C) launch_timed(wf_trace_fused<P, QUADS, L, TALLY, C>, tb, plan.dyn, n, stream, sc, cam, a)
+  switch (plan.lane) {
+    case kLaneWave: return RT_LDS(true, kLaneWave, true);
+    case kLaneWideLds: return cam_rays ? RT_LDS(false, kLaneWideLds, true) : RT_LDS(false, kLaneWideLds, false);
+    case kLanePair: return cam_rays ? RT_LDS(false, kLanePair, true) : RT_LDS(false, kLanePair, false);
   }
-  if (tn.image == 0 && pair_lds_bytes(sc) <= kWfLdsLimit) {
-    // the pair layout in LDS (scenes whose four-wide image does not fit beside the distances);
-    // the light buffer's distances take what room is left
-    dyn = pair_lds_bytes(sc);
-    if (dl && dyn + dl <= kWfLdsLimit) {
-      a.lds_flags |= kLdsDeltas;
-      dyn += dl;
-    }
-    return cam_rays ? launch_lds(wf_trace_fused<false, QUADS, 14, TALLY, true>, dyn, n, stream, sc, cam, a, tb)
-                    : launch_lds(wf_trace_fused<false, QUADS, 14, TALLY, false>, dyn, n, stream, sc, cam, a, tb);
-  }
-  if (wide_ok) {
-    // the four-wide hierarchy: its 16-bit stack, then the light buffer's distances
-    // and/or a treelet of its top nodes in the room left
-    const size_t room = kWfLdsLimit - wide_stack_bytes(sc);
-    dyn = wide_stack_bytes(sc);
-    if (dl && dl <= room && (!tn.treelet || tn.treelet_deltas)) { a.lds_flags |= kLdsDeltas; dyn += dl; }
-    if (tn.treelet) {
-      a.n_top = (unsigned)std::min<size_t>((size_t)sc.n_bvhw, (kWfLdsLimit - dyn) / sizeof(BvhWide16));
-      dyn += (size_t)a.n_top * sizeof(BvhWide16);
-    }
-    return launch_global(4, QUADS, TALLY, cam_rays, sc, cam, a, dyn, n, stream, tb);
-  }
-  if (tn.image != 1 && sc.bvh_depth <= kLaneLdsDepth) {
-    const size_t room = kWfLdsLimit - (size_t)kLaneLdsDepth * kTraceBlock * 4;
-    // the room left beside the stack: the light buffer's distances and/or a treelet
-    const bool deltas = dl && dl <= room && (!tn.treelet || tn.treelet_deltas);
-    if (deltas) { a.lds_flags |= kLdsDeltas; dyn = dl; }
-    if (tn.treelet) {
-      a.n_top = (unsigned)std::min<size_t>((size_t)sc.n_bvh, (room - dyn) / sizeof(BvhNode));
-      dyn += (size_t)a.n_top * sizeof(BvhNode);
-    }
-    return launch_global(3, QUADS, TALLY, cam_rays, sc, cam, a, dyn, n, stream, tb);
-  }
-  if (dl && dl <= kWfLdsLimit) { a.lds_flags |= kLdsDeltas; dyn = dl; }
-  return launch_global(1, QUADS, TALLY, cam_rays, sc, cam, a, dyn, n, stream, tb);
+#undef RT_LDS
+  if (t_ev_start) ++t_ev_used;
+  return wf_launch_global(plan.lane, QUADS, TALLY, cam_rays, sc, cam, a, plan.dyn, n, stream, tb, t_ev_start, t_ev_stop);
 }
 static hipError_t launch_fused(const DevScene& sc, const DevCamera& cam, const WfArgs& a, bool primary, unsigned n,
-                               hipStream_t stream, bool tally, const WfTuning& tn) {
+                               hipStream_t stream, bool tally, const WfTuning& tn, WfImagePlan* ran) {
   // QUADS: solids outside the hierarchies, or the hierarchy over the other records
   const bool quads = sc.n_fx_quads > 0 || sc.n_obvh > 0 || sc.n_lbvh > 0;
   if (tally)
-    return quads ? launch_fused_q<true, true>(sc, cam, a, primary, n, stream, tn)
-                 : launch_fused_q<false, true>(sc, cam, a, primary, n, stream, tn);
-  return quads ? launch_fused_q<true, false>(sc, cam, a, primary, n, stream, tn)
-               : launch_fused_q<false, false>(sc, cam, a, primary, n, stream, tn);
+    return quads ? launch_fused_q<true, true>(sc, cam, a, primary, n, stream, tn, ran)
+                 : launch_fused_q<false, true>(sc, cam, a, primary, n, stream, tn, ran);
+  return quads ? launch_fused_q<true, false>(sc, cam, a, primary, n, stream, tn, ran)
+               : launch_fused_q<false, false>(sc, cam, a, primary, n, stream, tn, ran);
 }
 
 // The launch arguments every launch of a pass shares: the job's tiling and
@@ -502,7 +423,7 @@ hipError_t Wavefront::render(const DevScene& sc, const WfJob& job, hipStream_t s
     n0 = n_frames * ((n0 + 63u) & ~63u);
   }
   const bool use_prim = camera_mode && sc.n_diag > 0 &&
-                        (fused || wf_lds_bytes(sc.n_diag, sc.n_gen, sc.n_planes, true) <= kWfLdsLimit);
+                        (fused || wf_lds_bytes(sc.n_diag, sc.n_gen, sc.n_planes, true) <= kFusedLdsLimit);
   {  // counters zeroed, generation 0 placed and the primary records written by one launch
     static_assert(sizeof(WfCounters) % 16 == 0, "WfCounters is zeroed in 16-B words");
     const unsigned n_a = (unsigned)(sizeof(WfCounters) / 16);
@@ -520,6 +441,7 @@ hipError_t Wavefront::render(const DevScene& sc, const WfJob& job, hipStream_t s
   prof_rays_[0] = prof_rays_[1] = prof_rays_[2] = 0;
   last_bvh_ = bvh;
   last_fused_ = fused;
+  plan_primary_ = plan_secondary_ = WfImagePlan{};
   lr_.stream = stream;
   lr_.fused = fused;
   if (fused)
@@ -640,7 +562,8 @@ hipError_t Wavefront::render_fast(const DevScene& sc, const WfJob& job, unsigned
     a.disc_slot = (unsigned)ccls;
     if (g == 0) prof_rays_[ccls] += n_real;
     WF_CHECK(pmark(stream, ccls, true));
-    WF_CHECK(launch_fused(sc, cam, a, prim_launch, g == 0 ? n0 : kAnyRays, stream, count, tn));
+    WF_CHECK(launch_fused(sc, cam, a, prim_launch, g == 0 ? n0 : kAnyRays, stream, count, tn,
+                          g == 0 ? &plan_primary_ : &plan_secondary_));
     WF_CHECK(pmark(stream, ccls, false));
     if (job.gen_ev && (int)g == job.gen_ev_g) {
       WF_CHECK(hipEventRecord(job.gen_ev, stream));
@@ -694,8 +617,8 @@ hipError_t Wavefront::render_exhaustive(const DevScene& sc, const WfJob& job, hi
     WF_CHECK(hipMemcpy2DAsync(gens_[0].rays, sizeof(WfRay), job.d_in_rays, 6 * sizeof(double), 6 * sizeof(double), n0,
                               hipMemcpyDeviceToDevice, stream));
   }
-  const bool prim_lds = wf_lds_bytes(sc.n_diag, sc.n_gen, sc.n_planes, true) <= kWfLdsLimit;
-  const bool gen_lds = wf_lds_bytes(sc.n_diag, sc.n_gen, sc.n_planes, false) <= kWfLdsLimit;
+  const bool prim_lds = wf_lds_bytes(sc.n_diag, sc.n_gen, sc.n_planes, true) <= kFusedLdsLimit;
+  const bool gen_lds = wf_lds_bytes(sc.n_diag, sc.n_gen, sc.n_planes, false) <= kFusedLdsLimit;
   const bool use_prim = camera_mode && prim_lds && sc.n_diag > 0;
   // Shadow traces of generation g depend only on closest(g), like closest(g+1);
   // they run on the side stream, forked after closest(g) and joined before the

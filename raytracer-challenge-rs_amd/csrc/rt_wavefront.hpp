@@ -80,9 +80,6 @@ struct PrimRec {  // primary rays share the origin: per diag sphere (s, o', c)
 };
 
 constexpr int kMaxGen = 66;
-// LDS a fused trace launch may take (of the CU's 160 KB)
-constexpr size_t kFusedLdsLimit = 160 * 1024 - 1024;
-constexpr int kFusedBlockThreads = 1024;  // threads of a fused trace block (kTraceBlock, rt_trace.hpp)
 enum WfFlags : unsigned { WF_EXHAUSTIVE = 1u, WF_COUNT = 2u, WF_TIME = 4u };  // WF_TIME: events around the render (kernel_ms)
 
 // Render-time tuning of a scene (rt_scene::tune, copied from the process
@@ -124,7 +121,16 @@ struct WfTuning {
 // Applies `key` = `value` to `t`: 1 = applied, 0 = not a render-time key, -1 = bad value.
 int wf_tuning_apply(WfTuning& t, const char* key, int value);
 
-// The fast path's launch over a global-memory scene image (lane 3 or 1) of
+// The scene image of one fused launch of the fast path (wf_plan_image,
+// rt_wf_plan.hpp): wf_trace_fused's LANE (-1: no fused launch), what it stages
+// in LDS (WfArgs::lds_flags, n_top) and the dynamic LDS it asks for.
+struct WfImagePlan {
+  int lane = -1;
+  unsigned lds_flags = 0, n_top = 0;
+  size_t dyn = 0;
+};
+
+// The fast path's launch over a global-memory scene image (lane 4, 3 or 1) of
 // one generation: compiled into its own code object (rt_wavefront_glb.hip,
 // built without the scheduler's trackers). e0/e1: launch-carried profiling
 // events, or null.
@@ -383,6 +389,7 @@ struct WfProfile {
   double sh_rays[2], sh_tests[2];  // fused frames: shadow rays / sphere tests inside the primary / secondary launches
   int bvh;          // the last frame traversed the BVH
   int fused;        // the last frame ran the fused pipeline
+  int lane_primary, lane_secondary;  // ... over these images: generation 0's, the last deeper one's (-1: none)
 };
 
 class Wavefront {
@@ -478,6 +485,8 @@ class Wavefront {
   // generation counts of the last render (fast path: from the host-mapped record; synchronises)
   hipError_t last_counts(std::vector<unsigned>& rays);
   bool last_bvh_ = false, last_fused_ = false;
+  // the last render's fused launches: generation 0's image, the last deeper generation's (lane -1: none)
+  WfImagePlan plan_primary_, plan_secondary_;
   bool gen_ev_done_ = false;  // gen_event_recorded()
   bool profiling_ = false;
   int pmask_ = (1 << WF_NCLASS) - 1;

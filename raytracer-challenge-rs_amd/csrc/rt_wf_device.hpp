@@ -772,8 +772,7 @@ __device__ __forceinline__ void shade_fused(const DevScene& sc, const DevCamera&
 // CAM: the launch may read camera rays (generation 0 of a camera render).
 template <bool PRIMARY, bool QUADS, int LANE, bool TALLY, bool CAM = PRIMARY>
 __global__ __launch_bounds__(kTraceBlock, 4) void wf_trace_fused(DevScene sc, DevCamera cam, WfArgs a) {
-  __shared__ int stack_lds[LANE == 3 ? kLaneLdsDepth * kTraceBlock
-                           : LANE == 0 ? (kTraceBlock / 64) * (kBvhMaxDepth + 4) : 1];
+  __shared__ int stack_lds[lane_static_lds_bytes(LANE) ? lane_static_lds_bytes(LANE) / 4 : 1];  // (1: never read)
   extern __shared__ __attribute__((aligned(16))) unsigned char lane_dyn[];
   int* stk = LANE == 0 ? stack_lds + (threadIdx.x / 64) * (kBvhMaxDepth + 4) : stack_lds + threadIdx.x;
   __shared__ unsigned s_pre[kPreRays];

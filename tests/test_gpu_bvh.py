@@ -242,6 +242,19 @@ def test_skipped_shadow_rays_bitwise(rt, neg_zero):
     assert full.to_numpy().tobytes() == exact.to_numpy().tobytes()
 
 
+def _expected_lane(p, image, wide, lds_wide):
+    """The scene image (wf_trace_fused's LANE, rt_wf_plan.hpp) the secondary
+    launches of a scene that fits in LDS run over, for these knob settings."""
+    if image == 1:
+        return 1  # binary nodes in global memory, scratch stack
+    if image == 0 and wide:
+        return 15 if lds_wide else 14  # the four-wide image / the pair layout in LDS
+    if image == 3 and wide:
+        return 4  # four-wide binary16 nodes in global memory
+    assert image == 3 and not wide
+    return 3 if p["bvh_depth"] <= 16 else 1  # binary nodes in global memory: LDS stack when the tree fits it
+
+
 @pytest.mark.parametrize("image,shadow_lb,wide,lds_wide", [
     (0, 1, 1, 0), (0, 0, 1, 0), (0, 1, 1, 1), (0, 0, 1, 1),
     (3, 1, 1, 0), (3, 0, 1, 0), (3, 1, 0, 0), (3, 0, 0, 0), (1, 1, 1, 0), (1, 0, 1, 0)])
@@ -263,6 +276,7 @@ def test_fused_images_bitwise(rt, image, shadow_lb, wide, lds_wide):
         p = rt._rtamd._wf_profile(w, -1, True)
         assert p["fused"]
         assert p["n_bvh_wide"] > 0 and p["wide_stack"] > 0
+        assert p["lane_secondary"] == _expected_lane(p, image, wide, lds_wide), p["lane_secondary"]
     finally:
         w.tune("image", 0)
         w.tune("shadow_lb", 1)
@@ -298,6 +312,8 @@ def test_wide_hierarchy_bitwise(rt, leaf):
             for lb in (1, 0):
                 w.tune("shadow_lb", lb)
                 fast, _ = cam.render(w, depth, want_stats=False)
+                p = rt._rtamd._wf_profile(w, -1, True)
+                assert p["lane_secondary"] == _expected_lane(p, image, wide, lds_wide), (image, wide, lb, p["lane_secondary"])
                 assert fast.to_numpy().tobytes() == exact.to_numpy().tobytes(), (wide, lb)
                 col, _ = w.color_at_batch(rays, depth, False)
                 assert col.tobytes() == col_exact.tobytes(), (wide, lb)
