@@ -85,6 +85,7 @@ extern "C" int rtamd_nccl_gather_f64(const double* send, double* recv, size_t co
 extern "C" int rtamd_nccl_comm_destroy(void* comm);
 extern "C" int rtamd_wf_profile(const rt_scene* s, int enable, double out[40]);
 extern "C" int rtamd_wf_gen_counts(const rt_scene* s, unsigned* out, int max);
+extern "C" int rtamd_wf_plan(const rt_scene* s, long long out[8]);
 extern "C" int rtamd_scene_tuning_set(const rt_scene* s, const char* key, int value);
 extern "C" int rtamd_render_shard_host(const rt_scene* scene, const rt_camera_desc* camera, uint32_t max_depth,
                                        uint32_t aa_samples, uint32_t row_block, uint32_t shard, uint32_t n_shards,
@@ -653,6 +654,25 @@ PYBIND11_MODULE(_rtamd, m) {
     }
     return d;
   }, py::arg("world"), py::arg("enable") = -1, py::arg("read") = true);
+  // the image plans of the last render's fused launches (rt_wf_plan.hpp): generation 0's and the
+  // last deeper generation's; lane -1 = none. lds_spheres / lds_deltas: the kLdsSpheres / kLdsDeltas flags
+  m.def("_wf_plan", [](const World& w) {
+    long long o[8] = {0};
+    check(rtamd_wf_plan(w.scene(), o), "wf_plan");
+    py::dict d;
+    const char* which[2] = {"primary", "secondary"};
+    for (int i = 0; i < 2; ++i) {
+      py::dict p;
+      p["lane"] = (int)o[4 * i];
+      p["lds_flags"] = (int)o[4 * i + 1];
+      p["lds_spheres"] = (o[4 * i + 1] & 1) != 0;
+      p["lds_deltas"] = (o[4 * i + 1] & 2) != 0;
+      p["n_top"] = o[4 * i + 2];
+      p["dyn"] = o[4 * i + 3];
+      d[which[i]] = p;
+    }
+    return d;
+  }, py::arg("world"));
   m.def("_tuning_set", [](const std::string& k, int v) { check(rtamd_tuning_set(k.c_str(), v), "tuning"); });
   m.def("_nccl_unique_id", []() {
     std::string id(128, '\0');

@@ -117,6 +117,25 @@ int rtamd_wf_profile(const rt_scene* cs, int enable, double out[40]) {
   return RT_OK;
 }
 
+// Development hook (not in the public ABI): the image plans (rt_wf_plan.hpp) of the scene's last
+// render's fused launches. out[0..3]: generation 0's lane, lds_flags, n_top, dyn; out[4..7]: the
+// last deeper generation's. Lane -1 (and zeros): no such launch, or the render was not fused.
+int rtamd_wf_plan(const rt_scene* cs, long long out[8]) {
+  if (!cs || !out) return fail(RT_ERR_INVALID_ARGUMENT, "null scene or output");
+  rt_scene* s = const_cast<rt_scene*>(cs);
+  std::lock_guard<std::mutex> lk(s->mu);
+  const WfImagePlan none{};
+  const WfImagePlan* pl[2] = {s->last_wf ? &s->last_wf->wf->plan_primary() : &none,
+                              s->last_wf ? &s->last_wf->wf->plan_secondary() : &none};
+  for (int i = 0; i < 2; ++i) {
+    out[4 * i] = pl[i]->lane;
+    out[4 * i + 1] = (long long)pl[i]->lds_flags;
+    out[4 * i + 2] = (long long)pl[i]->n_top;
+    out[4 * i + 3] = (long long)pl[i]->dyn;
+  }
+  return RT_OK;
+}
+
 // Rays of each generation of the scene's last render (dev tool): returns the
 // number of generations written into out[0 .. max).
 int rtamd_wf_gen_counts(const rt_scene* cs, unsigned* out, int max) {

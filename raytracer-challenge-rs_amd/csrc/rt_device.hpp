@@ -346,6 +346,25 @@ __device__ __forceinline__ void trace_rest(const DevScene& sc, V3 o, V3 d, Hit& 
   }
 }
 
+// The group gates trace_rest<.., QUADS, true> meets, without its tests: a counted
+// launch's ray that is answered before trace_rest runs (shadow_trace's `first`)
+// still owes the reference's count of the shapes its groups kept out.
+template <bool QUADS>
+__device__ __forceinline__ void count_rest_gates(const DevScene& sc, V3 o, V3 d, GateSkips& sk) {
+  if (!sc.n_groups) return;
+  cSphereGen sg = (cSphereGen)sc.fx_gen;
+  for (int j = 0; j < sc.n_fx_gen; ++j)
+    if (sg[j].gate && !group_gate(sc, sg[j].gate, o, d)) ++sk.sph;
+  cPlaneRec pl = (cPlaneRec)sc.planes;
+  for (int j = 0; j < sc.n_planes; ++j)
+    if (pl[j].gate && !group_gate(sc, pl[j].gate, o, d)) ++sk.plane;
+  if constexpr (QUADS) {
+    cQuadRec qr = (cQuadRec)sc.fx_quads;
+    for (int j = 0; j < sc.n_fx_quads; ++j)
+      if (qr[j].gate && !group_gate(sc, qr[j].gate, o, d)) ++sk.other;
+  }
+}
+
 // One culled other record (rt_layout.hpp OtherRec) with exactly the
 // operations of the exhaustive loops above: a general sphere as trace_rest's
 // general records, a solid as quad_test; a record inside groups only when the

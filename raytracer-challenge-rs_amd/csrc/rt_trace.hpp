@@ -940,7 +940,10 @@ __device__ __forceinline__ void lb_walk(const DevScene& sc, SD sd, const float* 
 // discriminant is negative or both roots negative, at margins eight orders
 // above its rounding: the reference's test of that sphere never reports a
 // blocker, and leaving it out changes no answer.
-template <int LANE, bool QUADS>
+// TALLY (a counted launch): a ray that `first` answers still counts the group
+// gates of the records it did not get to (count_rest_gates; the caller counts
+// the other hierarchy's, count_hier_gates).
+template <int LANE, bool QUADS, bool TALLY = false>
 __device__ __forceinline__ bool shadow_trace(const DevScene& sc, unsigned use_lb, const LaneScene& ls, unsigned l,
                                              V3 o, V3 d, double dist, unsigned& n_disc, unsigned& n_tests,
                                              unsigned& n_boxes, GateSkips* skips = nullptr, int first = -1,
@@ -951,7 +954,12 @@ __device__ __forceinline__ bool shadow_trace(const DevScene& sc, unsigned use_lb
     if constexpr (LANE == 14 || LANE == 15) leaf_sphere_test<true>(ls.s48, first, o, d, h, n_disc);
     else leaf_sphere_test<true>(ls.sd, first, o, d, h, n_disc);
     ++n_tests;
-    if (h.key >= 0 && h.t < dist) return true;
+    if (h.key >= 0 && h.t < dist) {
+      if constexpr (TALLY) {
+        if (skips) count_rest_gates<QUADS>(sc, o, d, *skips);
+      }
+      return true;
+    }
   }
   trace_rest<true, QUADS, true>(sc, o, d, h, n_disc, skips);
   if constexpr (QUADS) {

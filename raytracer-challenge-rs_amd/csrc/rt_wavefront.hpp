@@ -436,6 +436,10 @@ class Wavefront {
   // The last render recorded its job's gen_ev (a render with fewer generations,
   // or an exhaustive one, does not).
   bool gen_event_recorded() const { return gen_ev_done_; }
+  // The last render's fused launches (rtamd_wf_plan): generation 0's plan and the last deeper
+  // generation's (lane -1: the render had no such launch, or was not fused).
+  const WfImagePlan& plan_primary() const { return plan_primary_; }
+  const WfImagePlan& plan_secondary() const { return plan_secondary_; }
 
  private:
   // n0: the pass's generation-0 slots (a batch: n_frames x the padded frame), frame_real: one frame's root rays

@@ -669,8 +669,9 @@ struct FusedTally {
 // children (world.rs:107-134), shade_hit's lighting over the lights in order
 // (world.rs:40-56: one is_shadowed per light, a left fold from black), then
 // either the final colour (no children) or a ParentRec. Every lane of the wave
-// calls it (shard_append), `valid` false for the padding lanes.
-template <int LANE, bool QUADS, bool CAM>
+// calls it (shard_append), `valid` false for the padding lanes. TALLY: the
+// kernel's (a counted launch; shadow_trace then counts every group gate).
+template <int LANE, bool QUADS, bool CAM, bool TALLY>
 __device__ __forceinline__ void shade_fused(const DevScene& sc, const DevCamera& cam, const WfArgs& a,
                                             const LaneScene& ls, unsigned q, unsigned slot, bool valid, V3 o, V3 d,
                                             const Hit& h, FusedTally& t) {
@@ -739,9 +740,9 @@ __device__ __forceinline__ void shade_fused(const DevScene& sc, const DevCamera&
     if (a.skip_shadow && shadow_irrelevant(*m, Lr, sdir, c.normal, term)) {
       // the light is behind the surface: lighting() is the ambient term either way
     } else {
-      const bool shadowed = shadow_trace<LANE, QUADS>(sc, a.use_lb, ls, l, c.over, sdir, dist, t.sh_disc, t.sh_tests,
-                                                      t.sh_boxes, &t.gsk, own_first,
-                                                      own_out >= 0 && vdot(sdir, c.normal) >= 0.0 ? own_out : -1);
+      const bool shadowed = shadow_trace<LANE, QUADS, TALLY>(
+          sc, a.use_lb, ls, l, c.over, sdir, dist, t.sh_disc, t.sh_tests, t.sh_boxes, &t.gsk, own_first,
+          own_out >= 0 && vdot(sdir, c.normal) >= 0.0 ? own_out : -1);
       if (QUADS && a.count) count_hier_gates(sc, c.over, sdir, t.gsk);
       ++t.sh_rays;
       term = lighting(*m, Lr, c.over, c.eyev, c.normal, shadowed, sdir);
@@ -873,7 +874,7 @@ __global__ __launch_bounds__(kTraceBlock, 4) void wf_trace_fused(DevScene sc, De
     V3 o = v3(0, 0, 0), d = v3(0, 0, 0);
     Hit h;
     traverse(i, valid, slot, o, d, h);
-    shade_fused<LANE, QUADS, CAM>(sc, cam, a, ls, c, slot, valid, o, d, h, t);
+    shade_fused<LANE, QUADS, CAM, TALLY>(sc, cam, a, ls, c, slot, valid, o, d, h, t);
     c = dyn ? c_base + X * (unsigned)__shfl((int)k_next, 0, 64) : c + W;
   }
   if constexpr (!TALLY) return;
