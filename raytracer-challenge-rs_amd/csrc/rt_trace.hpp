@@ -1,8 +1,8 @@
 // rt_trace.hpp — device-side traversal and shading pieces of the generation
 // pipeline (rt_wavefront.hip): the exact-culling BVH traversals, the
-// light-buffer shadow walk, the per-block LDS scene image, and the small
-// shading helpers. Include only from .hip files compiled with
-// -ffp-contract=off.
+// fused kernel's scene images (one LaneImage type each: staging, records, walks),
+// the light-buffer shadow walk, and the small shading helpers. Include only from
+// .hip files compiled with -ffp-contract=off.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -122,17 +122,23 @@ __device__ __forceinline__ SlabRay slab_ray(V3 o, V3 d, const float* M) {
 // 2^-23 of x relative to it, and RN(f * (1 + 2^-22)) > f * (1 + 2^-23)
 // (0 and inf map to themselves).
 __device__ __forceinline__ float f32_up(double x) { return (float)x * (1.0f + 0x1p-22f); }
-// max(entry, 0) <= min(exit, t_hi): the ray may meet the box within [0, t_hi]
+// max(entry, t_lo) <= min(exit, t_hi): the ray may meet the box within [t_lo, t_hi]
 // (t_hi >= 0). `t_in` = the widened entry distance (child ordering only).
 template <typename P>  // P: constant-address (scalar loads) or generic (per-lane loads) float pointer
-__device__ __forceinline__ bool slab_hit32(P lo, P hi, const SlabRay& r, float t_hi, float& t_in) {
+__device__ __forceinline__ bool slab_hit32(P lo, P hi, const SlabRay& r, float t_hi, float& t_in, float t_lo = 0.0f) {
   const float x0 = fmaf(lo[0], r.inv[0], -r.c_lo[0]), x1 = fmaf(hi[0], r.inv[0], -r.c_hi[0]);
   const float y0 = fmaf(lo[1], r.inv[1], -r.c_lo[1]), y1 = fmaf(hi[1], r.inv[1], -r.c_hi[1]);
   const float z0 = fmaf(lo[2], r.inv[2], -r.c_lo[2]), z1 = fmaf(hi[2], r.inv[2], -r.c_hi[2]);
-  const float tmin = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), 0.0f));
+  const float tmin = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), t_lo));
   const float tmax = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fminf(fmaxf(z0, z1), t_hi));
   t_in = tmin;
   return tmin <= tmax;
+}
+// slab_ray's M of a hierarchy: the root's two child boxes contain every box below them.
+template <typename P>  // P: constant-address or generic node pointer
+__device__ __forceinline__ void root_bound(P root, float M[3]) {
+  for (int a = 0; a < 3; ++a)
+    M[a] = fmaxf(fmaxf(fabsf(root->lo[0][a]), fabsf(root->hi[0][a])), fmaxf(fabsf(root->lo[1][a]), fabsf(root->hi[1][a])));
 }
 
 template <bool PRIMARY, bool SHADOW>
@@ -141,9 +147,7 @@ __device__ __forceinline__ void bvh_trace(const DevScene& sc, cPrimRec prim, int
   hit_init(h);
   const cBvhNode nodes = (cBvhNode)sc.bvh;
   float M[3];
-  for (int a = 0; a < 3; ++a)
-    M[a] = fmaxf(fmaxf(fabsf(nodes->lo[0][a]), fabsf(nodes->hi[0][a])),
-                 fmaxf(fabsf(nodes->lo[1][a]), fabsf(nodes->hi[1][a])));
+  root_bound(nodes, M);
   const SlabRay sr = slab_ray(o, d, M);
   const float t_sh = SHADOW ? f32_up(t_shadow) : 0.0f;
   const cSphereDiag sd = (cSphereDiag)sc.sph_diag;
@@ -211,8 +215,8 @@ __device__ __forceinline__ void leaf_sphere_test(const SphereDiag* sd, int k, V3
   sphere_test<SHADOW>(s0 * o.x + r.t[0], s1 * o.y + r.t[1], s2 * o.z + r.t[2], s0 * d.x, s1 * d.y, s2 * d.z,
                       [&] { return (int)r.meta; }, h, n_disc);
 }
-// The pair image's LDS copy of the sphere records (lane_scene, LANE 14): 48 B
-// per record (s[3], t[3]) and the metas apart, 52 B instead of 64.
+// The LDS images' copy of the sphere records (stage_sph48): 48 B per record
+// (s[3], t[3]) and the metas apart, 52 B instead of 64.
 struct Sph48 {
   const double* r;   // 6 doubles per record
   const int* meta;
@@ -290,7 +294,10 @@ __device__ __forceinline__ void lane_trace(const BvhNode* nodes, const SphereDia
   // a leaf postpones it and keeps visiting nodes; the node phase ends when no
   // lane without a postponed leaf has a node left, then all postponed leaves
   // are tested together. Culling only ever uses the lane's current bound, so
-  // the postponement changes no result.
+  // the postponement changes no result. (lane_trace_wide and lane_trace_pair
+  // write the same loop out with their own codes: one shared driver taking the
+  // predicates and the visit / leaf / pop steps cost every per-lane image 1-4 %,
+  // profiles/image_types_refactor_ab.txt.)
   int pl = kBvhEmpty;
   for (;;) {
     for (;;) {
@@ -306,8 +313,8 @@ __device__ __forceinline__ void lane_trace(const BvhNode* nodes, const SphereDia
   }
 }
 // Per-lane traversal over the four-wide layout (NODE: BvhWide, 128-B binary32
-// nodes, LANE 15 with the whole image in LDS; BvhWide16, 64-B binary16 nodes,
-// LANE 4 from global memory with a treelet in LDS): a visit loads the parts of
+// nodes, kLaneWideLds with the whole image in LDS; BvhWide16, 64-B binary16 nodes,
+// kLaneWide16 from global memory with a treelet in LDS): a visit loads the parts of
 // the node it needs (per axis the block of the four entry planes and the block
 // of the four exit planes, chosen by the sign of the ray's direction there as
 // in lane_trace_pair, whose byte offsets sit packed in two registers: six 16-B
@@ -332,7 +339,7 @@ __device__ __forceinline__ void lane_trace(const BvhNode* nodes, const SphereDia
 // record, as a walk that culls nothing would. Leaves are batched across the
 // wave as in lane_trace.
 // SD: the sphere records (const SphereDiag* in global memory, or Sph48 in LDS);
-// ALL_LDS: every node is in `top` (LANE 15: the whole hierarchy in LDS).
+// ALL_LDS: every node is in `top` (kLaneWideLds: the whole hierarchy in LDS).
 template <bool SHADOW, typename SD = const SphereDiag*, bool ALL_LDS = false, typename NODE = BvhWide>
 __device__ __forceinline__ void lane_trace_wide(const NODE* nodes, SD sd, const float* M,
                                                 bool has_bvh, V3 o, V3 d, double t_shadow, Hit& h, unsigned& n_disc,
@@ -453,7 +460,7 @@ __device__ __forceinline__ void lane_trace_wide(const NODE* nodes, SD sd, const 
   }
 }
 
-// Per-lane traversal over the pair layout (LANE == 14): the block's LDS copy
+// Per-lane traversal over the pair layout (kLanePair): the block's LDS copy
 // of each binary node stores, per axis, the two children's lower bounds as
 // one 8-B pair and their upper bounds as the next pair (lo0 lo1 hi0 hi1 per
 // axis, then the child codes). Which face a ray enters on an axis follows the
@@ -464,16 +471,18 @@ __device__ __forceinline__ void lane_trace_wide(const NODE* nodes, SD sd, const 
 // ones lane_trace computes (entry = fma(entry face, inv, -on), exit =
 // fma(exit face, inv, -of), where lane_trace's min/max picks exactly them), so
 // the culling and the visit order are the same bit for bit. Leaves are
-// batched across the wave as in lane_trace<..., WW>.
+// batched across the wave as in lane_trace.
 // The pair image's child codes are 16-bit (rt_layout.hpp BvhPair: a node
 // index below 0x8000, a leaf 0x8000 | first << 3 | (count - 1), 0xFFFF
 // empty), so the per-lane LDS stack holds 16-bit entries.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int kPairEmpty = 0xFFFF;
 template <bool SHADOW>
-__device__ __forceinline__ void lane_trace_pair(const unsigned char* nodes, Sph48 sd, const float* M,
+__device__ __forceinline__ void lane_trace_pair(const BvhPair* nodes, Sph48 sd, const float* M,
                                                 bool has_bvh, V3 o, V3 d, double t_shadow, Hit& h, unsigned& n_disc,
                                                 unsigned& n_tests, unsigned& n_boxes, uint16_t* lds) {
+  // (slab_ray's values, derived here directly: recovering `on` and `of` from its c_lo / c_hi, as
+  // lane_trace_wide does, gives the same values and cost this image 0.4-0.9 %)
   float inv[3], on[3], of[3];
   int ent[3], ext[3];
   {
@@ -511,7 +520,7 @@ __device__ __forceinline__ void lane_trace_pair(const unsigned char* nodes, Sph4
   auto pop = [&]() { return (int)stk(--sp); };
   int e = (SHADOW && h.key >= 0 && h.t < t_shadow) || !has_bvh ? kPairEmpty : 0;
   auto visit = [&]() {
-    const unsigned char* nb = nodes + (size_t)e * 64;
+    const unsigned char* nb = (const unsigned char*)nodes + (size_t)e * sizeof(BvhPair);
     const f32x2 ex = *(const f32x2*)(nb + ent[0]), ey = *(const f32x2*)(nb + ent[1]), ez = *(const f32x2*)(nb + ent[2]);
     const f32x2 xx = *(const f32x2*)(nb + ext[0]), xy = *(const f32x2*)(nb + ext[1]), xz = *(const f32x2*)(nb + ext[2]);
     const int2 cc = *(const int2*)(nb + 48);
@@ -595,9 +604,7 @@ __device__ __forceinline__ void other_trace(const DevScene& sc, V3 o, V3 d, doub
   if (sc.n_obvh == 0 || (SHADOW && h.key >= 0 && h.t < t_shadow)) return;
   const BvhNode* nodes = sc.obvh;
   float M[3];
-  for (int ax = 0; ax < 3; ++ax)  // the root's two child boxes contain every box below them
-    M[ax] = fmaxf(fmaxf(fabsf(nodes[0].lo[0][ax]), fabsf(nodes[0].hi[0][ax])),
-                  fmaxf(fabsf(nodes[0].lo[1][ax]), fabsf(nodes[0].hi[1][ax])));
+  root_bound(nodes, M);
   const SlabRay sr = slab_ray(o, d, M);
   float t_hi = f32_up(SHADOW ? t_shadow : h.t);
   int stk[kBvhMaxDepth + 4];
@@ -684,20 +691,10 @@ __device__ __forceinline__ void line_trace(const DevScene& sc, V3 o, V3 d, doubl
   if (SHADOW && h.key >= 0 && h.t < t_shadow) return;
   const BvhNode* nodes = sc.lbvh;
   float M[3];
-  for (int ax = 0; ax < 3; ++ax)  // the root's two child boxes contain every box below them
-    M[ax] = fmaxf(fmaxf(fabsf(nodes[0].lo[0][ax]), fabsf(nodes[0].hi[0][ax])),
-                  fmaxf(fabsf(nodes[0].lo[1][ax]), fabsf(nodes[0].hi[1][ax])));
+  root_bound(nodes, M);
   const SlabRay sr = slab_ray(o, d, M);
   const float t_lo = SHADOW ? 0.0f : -INFINITY;
   float t_hi = f32_up(SHADOW ? t_shadow : h.t);
-  auto box = [&](const float* lo, const float* hi) {  // slab_hit32's test over [t_lo, t_hi]
-    const float x0 = fmaf(lo[0], sr.inv[0], -sr.c_lo[0]), x1 = fmaf(hi[0], sr.inv[0], -sr.c_hi[0]);
-    const float y0 = fmaf(lo[1], sr.inv[1], -sr.c_lo[1]), y1 = fmaf(hi[1], sr.inv[1], -sr.c_hi[1]);
-    const float z0 = fmaf(lo[2], sr.inv[2], -sr.c_lo[2]), z1 = fmaf(hi[2], sr.inv[2], -sr.c_hi[2]);
-    const float tmin = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), t_lo));
-    const float tmax = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fminf(fmaxf(z0, z1), t_hi));
-    return tmin <= tmax;
-  };
   int stk[kBvhMaxDepth + 4];
   int sp = 0, e = 0;
   while (e != kBvhEmpty) {
@@ -707,7 +704,8 @@ __device__ __forceinline__ void line_trace(const DevScene& sc, V3 o, V3 d, doubl
       const int32_t code = nd.child[c];
       if (code == kBvhEmpty) continue;
       ++n_boxes;
-      if (!box(nd.lo[c], nd.hi[c])) continue;
+      float t_in;
+      if (!slab_hit32(nd.lo[c], nd.hi[c], sr, t_hi, t_in, t_lo)) continue;
       if (code >= 0) { next[nn++] = code; continue; }
       const int lc = -(code + 1), first = lc >> 7, cnt = lc & 127;
       for (int k = first; k < first + cnt; ++k) {
@@ -745,123 +743,211 @@ __device__ __forceinline__ void count_hier_gates(const DevScene& sc, V3 o, V3 d,
   }
 }
 
-struct LaneScene {
-  const unsigned char* nodes;  // pair layout in LDS (14) or BvhNode[] in global memory
-  const SphereDiag* sd;        // sphere records (LDS or global; not LANE 14)
-  Sph48 s48;                   // LANE 14: the sphere records in LDS
-  uint16_t* stack16;           // LANE 14: the per-lane 16-bit LDS stack
-  const float* delta;          // light buffer: per-light box distances (global)
-  const _Float16* delta16;     // ... their binary16 lower bounds in LDS (when staged), else null
-  int* stack;                  // per-lane LDS stack (14, 3) or the wave's stack (0)
-  float M[3];                  // bound on |box coordinate| per axis (slab_ray)
-  const BvhNode* top;          // 3: the LDS copy of the first n_top nodes
-  int n_top;
-  const BvhWide* wtop;         // 15: the LDS copy of the wide nodes
-  const BvhWide16* wtop16;     // 4: the LDS copy of the first n_top binary16 wide nodes
-};
-// Stages the block's LDS image. The regions it walks over are those of
-// lane_lds_layout (rt_wf_plan.hpp), by which the host sizes the launch's dynamic
-// LDS; tests/cpp/plan_check.cpp holds this walk and that layout together. (Taking
-// the offsets from the layout here moves instructions in every image's kernel.)
-template <int LANE>
-__device__ __forceinline__ LaneScene lane_scene(const DevScene& sc, unsigned lds_flags, unsigned n_top, int* static_stack,
-                                                unsigned char* dyn) {
-  LaneScene ls{(const unsigned char*)sc.bvh, sc.sph_diag, Sph48{nullptr, nullptr}, nullptr, sc.lb_delta, nullptr,
-               static_stack, {0.f, 0.f, 0.f}, nullptr, 0, nullptr, nullptr};
-  unsigned char* p = dyn;
-  if constexpr (LANE == 15) {  // [16-bit stack][every wide node][Sph48 records and metas]
-    ls.stack16 = (uint16_t*)dyn + threadIdx.x;
-    p += wide_stack_bytes(sc);
-    stage_lds((uint4*)p, (const uint4*)sc.bvhw, sc.n_bvhw * (int)(sizeof(BvhWide) / 16));
-    ls.wtop = (const BvhWide*)p;
-    ls.nodes = p;
-    ls.n_top = sc.n_bvhw;
-    p += (size_t)sc.n_bvhw * sizeof(BvhWide);
-    uint4* r = (uint4*)p;
-    const uint4* src = (const uint4*)sc.sph_diag;
-    const int n3 = sc.n_diag * 3, bd = (int)blockDim.x;
-    for (int i = (int)threadIdx.x; i < n3; i += bd) {
-      const int k = i / 3;
-      r[i] = src[4 * k + (i - 3 * k)];
-    }
-    int* mt = (int*)(p + (size_t)sc.n_diag * 48);
-    for (int k = (int)threadIdx.x; k < sc.n_diag; k += bd) mt[k] = (int)sc.sph_diag[k].meta;
-    ls.s48 = Sph48{(const double*)p, (const int*)mt};
-    p += sph48_lds_bytes(sc);
-  }
-  if constexpr (LANE == 4) {  // [16-bit stack][distances][treelet of binary16 wide nodes]
-    ls.stack16 = (uint16_t*)dyn + threadIdx.x;
-    p += wide_stack_bytes(sc);
-    ls.nodes = (const unsigned char*)sc.bvhw16;
-    if (n_top > 0) {
-      unsigned char* q = p + ((lds_flags & kLdsDeltas) ? delta_lds_bytes(sc) : 0);
-      stage_lds((uint4*)q, (const uint4*)sc.bvhw16, (int)n_top * (int)(sizeof(BvhWide16) / 16));
-      ls.wtop16 = (const BvhWide16*)q;
-      ls.n_top = (int)n_top;
-    }
-  }
-  if constexpr (LANE == 14) {
-    // pair layout (BvhPair): per axis, the two children's lower bounds form one
-    // 8-B pair and their upper bounds the next (lane_trace_pair)
-    ls.stack16 = (uint16_t*)dyn + threadIdx.x;
-    p += (lane_stack_bytes(sc.bvh_depth + 1) / 2 + 15) & ~(size_t)15;
-    stage_lds((uint4*)p, (const uint4*)sc.bvh_pair, sc.n_bvh * (int)(sizeof(BvhPair) / 16));
-    ls.nodes = p;
-    p += (size_t)sc.n_bvh * sizeof(BvhPair);
-    // the sphere records, 48 B each (three of a SphereDiag's four 16-B chunks), and the metas
-    {
-      uint4* r = (uint4*)p;
-      const uint4* src = (const uint4*)sc.sph_diag;
-      const int n3 = sc.n_diag * 3, bd = (int)blockDim.x;
-      for (int i = (int)threadIdx.x; i < n3; i += bd) {
-        const int k = i / 3;
-        r[i] = src[4 * k + (i - 3 * k)];
+// ------------------------------------------------------------ scene images
+// The scene image a fused launch runs over (wf_trace_fused's LANE, the lane constants of
+// rt_wf_plan.hpp): one type per image, LaneImage<LANE>, with only what its walks read.
+//   stage(sc, lds_flags, n_top, static_stack, dyn)  block-wide: fills the image's regions of the
+//       block's dynamic LDS `dyn`, at lane_lds_layout's offsets (by which the host sized it), and
+//       synchronises; `static_stack` is the kernel's static LDS array
+//   sd                           the sphere records, as lb_walk and leaf_sphere_test take them
+//   walk<SHADOW>(sc, o, d, ...)  the shadow walk and, where kPerLane, the closest-hit walk into the
+//       hit it is given; the wave image finds its closest hit from scratch, closest()
+// Every image holds the light buffer's distances and slab_ray's M:
+struct LaneImageBase {
+  const float* delta;       // light buffer: per-light box distances (global)
+  const _Float16* delta16;  // ... their binary16 lower bounds in LDS (when staged), else null
+  float M[3];               // bound on |box coordinate| per axis (slab_ray)
+  // the end of every stage(): the distances into `ld` when lds_flags asks, the barrier, M
+  __device__ __forceinline__ void stage_shared(const DevScene& sc, unsigned lds_flags, unsigned char* ld_at) {
+    delta = sc.lb_delta;
+    delta16 = nullptr;
+    if (lds_flags & kLdsDeltas) {
+      // binary16 lower bounds: a positive value rounded toward zero (= down), anything
+      // else 0 (a stored 0 never ends a walk: the walk compares with a positive distance)
+      _Float16* ld = (_Float16*)ld_at;
+      auto down16 = [](float v) -> _Float16 { return v > 0.0f ? __builtin_amdgcn_cvt_pkrtz(v, 0.0f)[0] : (_Float16)0.0f; };
+      const int nd = sc.n_lights * sc.n_diag, bd = (int)blockDim.x;
+      int i = (int)threadIdx.x;
+      for (; i + 7 * bd < nd; i += 8 * bd) {  // eight loads in flight per thread
+        float v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = sc.lb_delta[i + k * bd];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) ld[i + k * bd] = down16(v[k]);
       }
-      int* mt = (int*)(p + (size_t)sc.n_diag * 48);
-      for (int k = (int)threadIdx.x; k < sc.n_diag; k += bd) mt[k] = (int)sc.sph_diag[k].meta;
-      ls.s48 = Sph48{(const double*)p, (const int*)mt};
-      p += sph48_lds_bytes(sc);
+      for (; i < nd; i += bd) ld[i] = down16(sc.lb_delta[i]);
+      delta16 = ld;
     }
+    __syncthreads();
+    M[0] = M[1] = M[2] = 0.0f;
+    if (sc.n_bvh > 0) root_bound(sc.bvh, M);
   }
-  if (LANE == 0 && (lds_flags & kLdsSpheres)) {
-    stage_lds((uint4*)p, (const uint4*)sc.sph_diag, sc.n_diag * (int)(sizeof(SphereDiag) / 16));
-    ls.sd = (const SphereDiag*)p;
-    p += sph_lds_bytes(sc);
+};
+// The 48-B sphere records (three of a SphereDiag's four 16-B chunks) and the metas
+// of the LDS images, staged at `p` (sph48_lds_bytes); the caller synchronises.
+__device__ __forceinline__ Sph48 stage_sph48(const DevScene& sc, unsigned char* p) {
+  uint4* r = (uint4*)p;
+  const uint4* src = (const uint4*)sc.sph_diag;
+  const int n3 = sc.n_diag * 3, bd = (int)blockDim.x;
+  for (int i = (int)threadIdx.x; i < n3; i += bd) {
+    const int k = i / 3;
+    r[i] = src[4 * k + (i - 3 * k)];
   }
-  if (LANE == 3 && n_top > 0) {  // the treelet: after the distances when those are staged
-    unsigned char* q = p + ((lds_flags & kLdsDeltas) ? delta_lds_bytes(sc) : 0);
-    stage_lds((uint4*)q, (const uint4*)sc.bvh, (int)n_top * (int)(sizeof(BvhNode) / 16));
-    ls.top = (const BvhNode*)q;
-    ls.n_top = (int)n_top;
-  }
-  if (lds_flags & kLdsDeltas) {
-    // binary16 lower bounds: a positive value rounded toward zero (= down), anything
-    // else 0 (a stored 0 never ends a walk: the walk compares with a positive distance)
-    _Float16* ld = (_Float16*)p;
-    auto down16 = [](float v) -> _Float16 { return v > 0.0f ? __builtin_amdgcn_cvt_pkrtz(v, 0.0f)[0] : (_Float16)0.0f; };
-    const int nd = sc.n_lights * sc.n_diag, bd = (int)blockDim.x;
-    int i = (int)threadIdx.x;
-    for (; i + 7 * bd < nd; i += 8 * bd) {  // eight loads in flight per thread
-      float v[8];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) v[k] = sc.lb_delta[i + k * bd];
-#pragma unroll
-      for (int k = 0; k < 8; ++k) ld[i + k * bd] = down16(v[k]);
-    }
-    for (; i < nd; i += bd) ld[i] = down16(sc.lb_delta[i]);
-    ls.delta16 = ld;
-  }
-  __syncthreads();
-  for (int ax = 0; ax < 3; ++ax) {  // the root's two child boxes contain every box below them
-    float m = 0.0f;
-    if (sc.n_bvh > 0) {
-      const BvhNode& r = sc.bvh[0];
-      m = fmaxf(fmaxf(fabsf(r.lo[0][ax]), fabsf(r.hi[0][ax])), fmaxf(fabsf(r.lo[1][ax]), fabsf(r.hi[1][ax])));
-    }
-    ls.M[ax] = m;
-  }
-  return ls;
+  int* mt = (int*)(p + (size_t)sc.n_diag * 48);
+  for (int k = (int)threadIdx.x; k < sc.n_diag; k += bd) mt[k] = (int)sc.sph_diag[k].meta;
+  return Sph48{(const double*)p, (const int*)mt};
 }
+
+template <int LANE>
+struct LaneImage;
+
+// the four-wide hierarchy, the 48-B sphere records and the 16-bit stack in LDS
+template <>
+struct LaneImage<kLaneWideLds> : LaneImageBase {
+  Sph48 sd;
+  const BvhWide* nodes;  // every node, in LDS
+  uint16_t* stack;       // the lane's 16-bit LDS stack
+  __device__ __forceinline__ void stage(const DevScene& sc, unsigned lds_flags, unsigned n_top, int* static_stack,
+                                        unsigned char* dyn) {
+    const LaneLdsLayout L = lane_lds_layout(kLaneWideLds, sc, lds_flags, n_top);
+    stack = (uint16_t*)(dyn + L.stack) + threadIdx.x;
+    stage_lds((uint4*)(dyn + L.nodes), (const uint4*)sc.bvhw, sc.n_bvhw * (int)(sizeof(BvhWide) / 16));
+    nodes = (const BvhWide*)(dyn + L.nodes);
+    sd = stage_sph48(sc, dyn + L.sph48);
+    stage_shared(sc, lds_flags, dyn + L.deltas);
+  }
+  static constexpr bool kPerLane = true;
+  template <bool SHADOW>
+  __device__ __forceinline__ void walk(const DevScene& sc, V3 o, V3 d, double t_shadow, Hit& h, unsigned& n_disc,
+                                       unsigned& n_tests, unsigned& n_boxes) const {
+    lane_trace_wide<SHADOW, Sph48, true>(nodes, sd, M, sc.bvhw != nullptr, o, d, t_shadow, h, n_disc, n_tests, n_boxes,
+                                         stack, nodes, sc.n_bvhw, sc.n_diag);
+  }
+};
+// pair-layout nodes (per axis, the two children's lower bounds form one 8-B pair and
+// their upper bounds the next), the 48-B sphere records and the 16-bit stack in LDS
+template <>
+struct LaneImage<kLanePair> : LaneImageBase {
+  Sph48 sd;
+  const BvhPair* nodes;  // every node, in LDS
+  uint16_t* stack;       // the lane's 16-bit LDS stack
+  __device__ __forceinline__ void stage(const DevScene& sc, unsigned lds_flags, unsigned n_top, int* static_stack,
+                                        unsigned char* dyn) {
+    const LaneLdsLayout L = lane_lds_layout(kLanePair, sc, lds_flags, n_top);
+    stack = (uint16_t*)(dyn + L.stack) + threadIdx.x;
+    stage_lds((uint4*)(dyn + L.nodes), (const uint4*)sc.bvh_pair, sc.n_bvh * (int)(sizeof(BvhPair) / 16));
+    nodes = (const BvhPair*)(dyn + L.nodes);
+    sd = stage_sph48(sc, dyn + L.sph48);
+    stage_shared(sc, lds_flags, dyn + L.deltas);
+  }
+  static constexpr bool kPerLane = true;
+  template <bool SHADOW>
+  __device__ __forceinline__ void walk(const DevScene& sc, V3 o, V3 d, double t_shadow, Hit& h, unsigned& n_disc,
+                                       unsigned& n_tests, unsigned& n_boxes) const {
+    lane_trace_pair<SHADOW>(nodes, sd, M, sc.n_bvh > 0, o, d, t_shadow, h, n_disc, n_tests, n_boxes, stack);
+  }
+};
+// binary16 four-wide nodes and the records in global memory; in LDS the 16-bit stack,
+// the distances and a treelet of the first n_top nodes
+template <>
+struct LaneImage<kLaneWide16> : LaneImageBase {
+  const SphereDiag* sd;
+  const BvhWide16* top;  // the LDS copy of the first n_top nodes
+  int n_top;
+  uint16_t* stack;       // the lane's 16-bit LDS stack
+  __device__ __forceinline__ void stage(const DevScene& sc, unsigned lds_flags, unsigned n_top, int* static_stack,
+                                        unsigned char* dyn) {
+    const LaneLdsLayout L = lane_lds_layout(kLaneWide16, sc, lds_flags, n_top);
+    sd = sc.sph_diag;
+    stack = (uint16_t*)(dyn + L.stack) + threadIdx.x;
+    stage_lds((uint4*)(dyn + L.treelet), (const uint4*)sc.bvhw16, (int)n_top * (int)(sizeof(BvhWide16) / 16));
+    top = (const BvhWide16*)(dyn + L.treelet);
+    this->n_top = (int)n_top;
+    stage_shared(sc, lds_flags, dyn + L.deltas);
+  }
+  static constexpr bool kPerLane = true;
+  template <bool SHADOW>
+  __device__ __forceinline__ void walk(const DevScene& sc, V3 o, V3 d, double t_shadow, Hit& h, unsigned& n_disc,
+                                       unsigned& n_tests, unsigned& n_boxes) const {
+    lane_trace_wide<SHADOW>(sc.bvhw16, sd, M, sc.bvhw16 != nullptr, o, d, t_shadow, h, n_disc, n_tests, n_boxes, stack,
+                            top, n_top, sc.n_diag);
+  }
+};
+// binary nodes and the records in global memory; the per-lane stack in static LDS, the
+// distances and a treelet of the first n_top nodes in dynamic LDS
+template <>
+struct LaneImage<kLaneLdsStack> : LaneImageBase {
+  const SphereDiag* sd;
+  const BvhNode* top;  // the LDS copy of the first n_top nodes
+  int n_top;
+  int* stack;          // the lane's LDS stack
+  __device__ __forceinline__ void stage(const DevScene& sc, unsigned lds_flags, unsigned n_top, int* static_stack,
+                                        unsigned char* dyn) {
+    const LaneLdsLayout L = lane_lds_layout(kLaneLdsStack, sc, lds_flags, n_top);
+    sd = sc.sph_diag;
+    stack = static_stack + threadIdx.x;
+    stage_lds((uint4*)(dyn + L.treelet), (const uint4*)sc.bvh, (int)n_top * (int)(sizeof(BvhNode) / 16));
+    top = (const BvhNode*)(dyn + L.treelet);
+    this->n_top = (int)n_top;
+    stage_shared(sc, lds_flags, dyn + L.deltas);
+  }
+  static constexpr bool kPerLane = true;
+  template <bool SHADOW>
+  __device__ __forceinline__ void walk(const DevScene& sc, V3 o, V3 d, double t_shadow, Hit& h, unsigned& n_disc,
+                                       unsigned& n_tests, unsigned& n_boxes) const {
+    lane_trace<SHADOW, true>(sc.bvh, sd, M, sc.n_bvh > 0, o, d, t_shadow, h, n_disc, n_tests, n_boxes, stack, top, n_top);
+  }
+};
+// binary nodes and the records in global memory, the per-lane stack in scratch (trees
+// deeper than kLaneLdsDepth); only the distances in LDS
+template <>
+struct LaneImage<kLaneScratch> : LaneImageBase {
+  const SphereDiag* sd;
+  __device__ __forceinline__ void stage(const DevScene& sc, unsigned lds_flags, unsigned n_top, int* static_stack,
+                                        unsigned char* dyn) {
+    sd = sc.sph_diag;
+    stage_shared(sc, lds_flags, dyn + lane_lds_layout(kLaneScratch, sc, lds_flags, n_top).deltas);
+  }
+  static constexpr bool kPerLane = true;
+  template <bool SHADOW>
+  __device__ __forceinline__ void walk(const DevScene& sc, V3 o, V3 d, double t_shadow, Hit& h, unsigned& n_disc,
+                                       unsigned& n_tests, unsigned& n_boxes) const {
+    lane_trace<SHADOW, false>(sc.bvh, sd, M, sc.n_bvh > 0, o, d, t_shadow, h, n_disc, n_tests, n_boxes, nullptr);
+  }
+};
+// primary rays: the wave (packet) traversal over global nodes with one static-LDS stack
+// per wave; the sphere records are staged in LDS for the shadow rays when they fit
+template <>
+struct LaneImage<kLaneWave> : LaneImageBase {
+  static constexpr bool kPerLane = false;
+  const SphereDiag* sd;  // in LDS with kLdsSpheres, else global
+  int* stack;            // the wave's stack
+  __device__ __forceinline__ void stage(const DevScene& sc, unsigned lds_flags, unsigned n_top, int* static_stack,
+                                        unsigned char* dyn) {
+    const LaneLdsLayout L = lane_lds_layout(kLaneWave, sc, lds_flags, n_top);
+    sd = sc.sph_diag;
+    stack = static_stack + (threadIdx.x / 64) * (kBvhMaxDepth + 4);
+    if (lds_flags & kLdsSpheres) {
+      stage_lds((uint4*)(dyn + L.sph), (const uint4*)sc.sph_diag, sc.n_diag * (int)(sizeof(SphereDiag) / 16));
+      sd = (const SphereDiag*)(dyn + L.sph);
+    }
+    stage_shared(sc, lds_flags, dyn + L.deltas);
+  }
+  // the closest hit, from scratch (it initialises h); `prim`: the frame's shared-origin records (PRIMARY)
+  template <bool PRIMARY>
+  __device__ __forceinline__ void closest(const DevScene& sc, cPrimRec prim, V3 o, V3 d, Hit& h, unsigned& n_disc,
+                                          unsigned& n_tests, unsigned& n_boxes) const {
+    bvh_trace<PRIMARY, false>(sc, prim, stack, o, d, 0.0, h, n_disc, n_tests, n_boxes);
+  }
+  template <bool SHADOW>
+  __device__ __forceinline__ void walk(const DevScene& sc, V3 o, V3 d, double t_shadow, Hit& h, unsigned& n_disc,
+                                       unsigned& n_tests, unsigned& n_boxes) const {
+    static_assert(SHADOW, "the wave image's closest-hit walk is closest()");
+    Hit hb;  // the wave traversal starts from an empty hit; any blocker is an answer
+    bvh_trace<false, true>(sc, nullptr, stack, o, d, t_shadow, hb, n_disc, n_tests, n_boxes);
+    if (hb.key >= 0 && hb.key != 0x7fffffff && hb.t < t_shadow) h = hb;
+  }
+};
 
 // World::is_shadowed for the diagonal spheres through the light buffer
 // (DESIGN.md "Light buffer"): the cube-map cell of direction o - light lists
@@ -943,16 +1029,15 @@ __device__ __forceinline__ void lb_walk(const DevScene& sc, SD sd, const float* 
 // TALLY (a counted launch): a ray that `first` answers still counts the group
 // gates of the records it did not get to (count_rest_gates; the caller counts
 // the other hierarchy's, count_hier_gates).
-template <int LANE, bool QUADS, bool TALLY = false>
-__device__ __forceinline__ bool shadow_trace(const DevScene& sc, unsigned use_lb, const LaneScene& ls, unsigned l,
+template <bool QUADS, bool TALLY = false, typename Image>
+__device__ __forceinline__ bool shadow_trace(const DevScene& sc, unsigned use_lb, const Image& img, unsigned l,
                                              V3 o, V3 d, double dist, unsigned& n_disc, unsigned& n_tests,
                                              unsigned& n_boxes, GateSkips* skips = nullptr, int first = -1,
                                              int skip = -1) {
   Hit h;
   hit_init(h);
   if (first >= 0) {
-    if constexpr (LANE == 14 || LANE == 15) leaf_sphere_test<true>(ls.s48, first, o, d, h, n_disc);
-    else leaf_sphere_test<true>(ls.sd, first, o, d, h, n_disc);
+    leaf_sphere_test<true>(img.sd, first, o, d, h, n_disc);
     ++n_tests;
     if (h.key >= 0 && h.t < dist) {
       if constexpr (TALLY) {
@@ -967,27 +1052,8 @@ __device__ __forceinline__ bool shadow_trace(const DevScene& sc, unsigned use_lb
     line_trace<true>(sc, o, d, dist, h, n_tests, n_boxes);
   }
   if (!(h.key >= 0 && h.t < dist)) {
-    if (use_lb) {
-      if constexpr (LANE == 14 || LANE == 15) lb_walk(sc, ls.s48, ls.delta, ls.delta16, l, o, d, dist, h, n_disc, n_tests, skip);
-      else lb_walk(sc, ls.sd, ls.delta, ls.delta16, l, o, d, dist, h, n_disc, n_tests, skip);
-    } else if constexpr (LANE == 14) {
-      lane_trace_pair<true>(ls.nodes, ls.s48, ls.M, sc.n_bvh > 0, o, d, dist, h, n_disc, n_tests, n_boxes,
-                            ls.stack16);
-    } else if constexpr (LANE == 15) {
-      lane_trace_wide<true, Sph48, true>((const BvhWide*)ls.nodes, ls.s48, ls.M, sc.bvhw != nullptr, o, d, dist, h, n_disc,
-                                         n_tests, n_boxes, ls.stack16, ls.wtop, ls.n_top, sc.n_diag);
-    } else if constexpr (LANE == 4) {
-      lane_trace_wide<true>((const BvhWide16*)ls.nodes, ls.sd, ls.M, sc.bvhw16 != nullptr, o, d, dist, h, n_disc,
-                            n_tests, n_boxes, ls.stack16, ls.wtop16, ls.n_top, sc.n_diag);
-
-    } else if constexpr (LANE == 0) {
-      Hit hb;  // the wave traversal starts from an empty hit; any blocker is an answer
-      bvh_trace<false, true>(sc, nullptr, ls.stack, o, d, dist, hb, n_disc, n_tests, n_boxes);
-      if (hb.key >= 0 && hb.key != 0x7fffffff && hb.t < dist) h = hb;
-    } else {
-      lane_trace<true, LANE == 3>((const BvhNode*)ls.nodes, ls.sd, ls.M, sc.n_bvh > 0, o, d, dist, h, n_disc,
-                                  n_tests, n_boxes, ls.stack, ls.top, ls.n_top);
-    }
+    if (use_lb) lb_walk(sc, img.sd, img.delta, img.delta16, l, o, d, dist, h, n_disc, n_tests, skip);
+    else img.template walk<true>(sc, o, d, dist, h, n_disc, n_tests, n_boxes);
   }
   hit_finish(h);
   return h.key >= 0 && h.t < dist;

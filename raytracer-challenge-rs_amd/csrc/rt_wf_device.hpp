@@ -1,10 +1,11 @@
 // rt_wf_device.hpp — the wavefront pipeline's device code shared by its
-// translation units: queue appends and sharded slots, ray fetch, the LDS scene
-// image, the trace loops and the fused generation kernel (wf_trace_fused:
-// closest hit + shading + shadow rays + spawn). rt_wavefront.hip launches
-// them over the LDS images, rt_wavefront_glb.hip over the global-memory
-// images (its own code object); rt_wf_combine.hip holds the frame's other
-// kernels (frame init, combine, average).
+// translation units: queue appends and sharded slots, ray fetch, the exhaustive
+// trace loops over their LDS image, and the fused generation kernel
+// (wf_trace_fused: closest hit + shading + shadow rays + spawn over a LaneImage
+// of rt_trace.hpp). rt_wavefront.hip launches them over the LDS images,
+// rt_wavefront_glb.hip over the global-memory images (its own code object);
+// rt_wf_combine.hip holds the frame's other kernels (frame init, combine,
+// average).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -556,20 +557,8 @@ __device__ __forceinline__ void prep_one(const DevScene& sc, const WfArgs& a, un
 // node without children (a miss, a diffuse surface, the last generation), its
 // final colour. Only nodes with a reflected or refracted child are queued
 // (ParentRec) for wf_combine_parents, which runs once the children's colours
-// exist. Scene images of the kernels (LANE):
-//   15: the four-wide hierarchy + 48-B sphere records + 16-bit stack in LDS
-//       (the default where they fit)
-//   14: pair-layout nodes + sphere records + per-lane stack in LDS
-//    4: the four-wide hierarchy and records in global memory, a treelet of its
-//       top nodes and the 16-bit stack in LDS (the default for larger scenes)
-//    3: binary nodes and records in global memory, per-lane stack in LDS
-//    1: nodes and records in global memory, per-lane stack in scratch (trees
-//       deeper than kLaneLdsDepth)
-//    0: primary rays, wave (packet) traversal over global nodes (one LDS stack
-//       per wave); the sphere records are staged in LDS for the shadow rays
-//       when they fit
-// The per-light box distances of the light buffer are staged in LDS when they
-// fit beside the image (WfArgs::lds_flags).
+// exist. The scene image a launch runs over is the kernel's LANE, one type per
+// image: LaneImage<LANE> (rt_trace.hpp), chosen by wf_plan_image (rt_wf_plan.hpp).
 // Where generation g's colour of ray `slot` goes: generation 0 of a camera
 // render without AA is tile-ordered, and its colours are written row-major
 // into the output.
@@ -671,9 +660,9 @@ struct FusedTally {
 // either the final colour (no children) or a ParentRec. Every lane of the wave
 // calls it (shard_append), `valid` false for the padding lanes. TALLY: the
 // kernel's (a counted launch; shadow_trace then counts every group gate).
-template <int LANE, bool QUADS, bool CAM, bool TALLY>
+template <bool QUADS, bool CAM, bool TALLY, typename Image>
 __device__ __forceinline__ void shade_fused(const DevScene& sc, const DevCamera& cam, const WfArgs& a,
-                                            const LaneScene& ls, unsigned q, unsigned slot, bool valid, V3 o, V3 d,
+                                            const Image& img, unsigned q, unsigned slot, bool valid, V3 o, V3 d,
                                             const Hit& h, FusedTally& t) {
   const unsigned L = (unsigned)sc.n_lights;
   const unsigned remaining = a.max_depth - a.g;
@@ -740,8 +729,8 @@ __device__ __forceinline__ void shade_fused(const DevScene& sc, const DevCamera&
     if (a.skip_shadow && shadow_irrelevant(*m, Lr, sdir, c.normal, term)) {
       // the light is behind the surface: lighting() is the ambient term either way
     } else {
-      const bool shadowed = shadow_trace<LANE, QUADS, TALLY>(
-          sc, a.use_lb, ls, l, c.over, sdir, dist, t.sh_disc, t.sh_tests, t.sh_boxes, &t.gsk, own_first,
+      const bool shadowed = shadow_trace<QUADS, TALLY>(
+          sc, a.use_lb, img, l, c.over, sdir, dist, t.sh_disc, t.sh_tests, t.sh_boxes, &t.gsk, own_first,
           own_out >= 0 && vdot(sdir, c.normal) >= 0.0 ? own_out : -1);
       if (QUADS && a.count) count_hier_gates(sc, c.over, sdir, t.gsk);
       ++t.sh_rays;
@@ -775,7 +764,6 @@ template <bool PRIMARY, bool QUADS, int LANE, bool TALLY, bool CAM = PRIMARY>
 __global__ __launch_bounds__(kTraceBlock, 4) void wf_trace_fused(DevScene sc, DevCamera cam, WfArgs a) {
   __shared__ int stack_lds[lane_static_lds_bytes(LANE) ? lane_static_lds_bytes(LANE) / 4 : 1];  // (1: never read)
   extern __shared__ __attribute__((aligned(16))) unsigned char lane_dyn[];
-  int* stk = LANE == 0 ? stack_lds + (threadIdx.x / 64) * (kBvhMaxDepth + 4) : stack_lds + threadIdx.x;
   __shared__ unsigned s_pre[kPreRays];
   const unsigned* pre = shard_prefix<true>(a.in_cnt, s_pre);
   if (a.dev_sized) bind_generation(a, pre);
@@ -791,7 +779,9 @@ __global__ __launch_bounds__(kTraceBlock, 4) void wf_trace_fused(DevScene sc, De
   // in flight slower (WfTuning::spread, off by default; profiles/r06_spread.txt)
   const bool spread = a.spread && n_chunks < W;
   if (spread ? blockIdx.x >= n_chunks : blockIdx.x * waves_per_block >= n_chunks) return;
-  const LaneScene ls = lane_scene<LANE>(sc, a.lds_flags, a.n_top, stk, lane_dyn);
+  typedef LaneImage<LANE> Image;
+  Image img;
+  img.stage(sc, a.lds_flags, a.n_top, stack_lds, lane_dyn);
   FusedTally t;
   // Work distribution: chunk c = rays [64c, 64c + 64), one wave-iteration.
   // A launch with more chunks than waves hands them out dynamically from the
@@ -830,37 +820,19 @@ __global__ __launch_bounds__(kTraceBlock, 4) void wf_trace_fused(DevScene sc, De
     if (valid) {
       wf_ray<CAM>(a, cam, slot, o, d);
       if constexpr (TALLY && QUADS) count_hier_gates(sc, o, d, t.gsk);
-      if constexpr (LANE == 0) {
+      if constexpr (!Image::kPerLane) {
         // the chunk's frame (chunks never mix frames): its shared-origin primary records
         const unsigned pf = a.n_frames > 1 ? (c * 64u) / a.frame_rays : 0u;
-        bvh_trace<PRIMARY, false>(sc, (cPrimRec)(a.prim + (size_t)pf * ((unsigned)sc.n_diag + 4)), stk, o, d, 0.0, h,
-                                  t.disc, t.tests, t.boxes);
-        trace_rest<false, QUADS, true>(sc, o, d, h, t.disc, &t.gsk);
-        if constexpr (QUADS) {
-          other_trace<false>(sc, o, d, 0.0, h, t.disc, t.tests, t.boxes);
-          line_trace<false>(sc, o, d, 0.0, h, t.tests, t.boxes);
-        }
-      } else {
-        // planes and the other records first: an early nearest hit tightens the culling
-        trace_rest<false, QUADS, true>(sc, o, d, h, t.disc, &t.gsk);
-        if constexpr (QUADS) {
-          other_trace<false>(sc, o, d, 0.0, h, t.disc, t.tests, t.boxes);
-          line_trace<false>(sc, o, d, 0.0, h, t.tests, t.boxes);
-        }
-        if constexpr (LANE == 14) {
-          lane_trace_pair<false>(ls.nodes, ls.s48, ls.M, sc.n_bvh > 0, o, d, 0.0, h, t.disc, t.tests, t.boxes,
-                                 ls.stack16);
-        } else if constexpr (LANE == 15) {
-          lane_trace_wide<false, Sph48, true>((const BvhWide*)ls.nodes, ls.s48, ls.M, sc.bvhw != nullptr, o, d, 0.0, h,
-                                              t.disc, t.tests, t.boxes, ls.stack16, ls.wtop, ls.n_top, sc.n_diag);
-        } else if constexpr (LANE == 4) {
-          lane_trace_wide<false>((const BvhWide16*)ls.nodes, ls.sd, ls.M, sc.bvhw16 != nullptr, o, d, 0.0, h, t.disc,
-                                 t.tests, t.boxes, ls.stack16, ls.wtop16, ls.n_top, sc.n_diag);
-        } else {
-          lane_trace<false, LANE == 3>((const BvhNode*)ls.nodes, ls.sd, ls.M, sc.n_bvh > 0, o, d, 0.0, h, t.disc,
-                                       t.tests, t.boxes, ls.stack, ls.top, ls.n_top);
-        }
+        img.template closest<PRIMARY>(sc, (cPrimRec)(a.prim + (size_t)pf * ((unsigned)sc.n_diag + 4)), o, d, h, t.disc,
+                                      t.tests, t.boxes);
       }
+      // (a per-lane walk: planes and the other records first, an early nearest hit tightens the culling)
+      trace_rest<false, QUADS, true>(sc, o, d, h, t.disc, &t.gsk);
+      if constexpr (QUADS) {
+        other_trace<false>(sc, o, d, 0.0, h, t.disc, t.tests, t.boxes);
+        line_trace<false>(sc, o, d, 0.0, h, t.tests, t.boxes);
+      }
+      if constexpr (Image::kPerLane) img.template walk<false>(sc, o, d, 0.0, h, t.disc, t.tests, t.boxes);
     }
     hit_finish(h);
   };
@@ -874,7 +846,7 @@ __global__ __launch_bounds__(kTraceBlock, 4) void wf_trace_fused(DevScene sc, De
     V3 o = v3(0, 0, 0), d = v3(0, 0, 0);
     Hit h;
     traverse(i, valid, slot, o, d, h);
-    shade_fused<LANE, QUADS, CAM, TALLY>(sc, cam, a, ls, c, slot, valid, o, d, h, t);
+    shade_fused<QUADS, CAM, TALLY>(sc, cam, a, img, c, slot, valid, o, d, h, t);
     c = dyn ? c_base + X * (unsigned)__shfl((int)k_next, 0, 64) : c + W;
   }
   if constexpr (!TALLY) return;

@@ -1,8 +1,9 @@
 // rt_wf_plan.hpp — which scene image a fused launch of the fast path runs over
 // (wf_trace_fused's LANE) and how its block's dynamic LDS is laid out. The
-// host takes both from here (launch_fused_q asks for WfImagePlan::dyn bytes);
-// the kernel's lane_scene (rt_trace.hpp) walks the same regions with the size
-// functions below, and tests/cpp/plan_check.cpp holds its walk to this layout.
+// host takes both from here (launch_fused_q asks for WfImagePlan::dyn bytes),
+// and so does the kernel: each image's stage (rt_trace.hpp LaneImage) takes its
+// region offsets from lane_lds_layout; tests/cpp/plan_check.cpp holds the bytes
+// a stage writes into a region to the region's size.
 // Plain C++: a host compiler builds it with only the HIP headers on the include
 // path, so no device builtins and no _Float16 here (a binary16 value is 2 bytes).
 #pragma once

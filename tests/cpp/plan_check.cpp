@@ -1,10 +1,11 @@
 // Host check of rt_wf_plan.hpp (tests/test_image_plan.py): wf_plan_image and
 // lane_lds_layout against `old_rules`, the decision launch_fused_q made inline
 // before the plan existed (with the size functions it used), and against
-// `kernel_walk`, a transcription of the pointer walk lane_scene (rt_trace.hpp)
-// makes over the block's dynamic LDS. A sweep of synthetic scenes (the pointers
-// are dummies, never dereferenced) on both sides of every threshold; the
-// outcomes are counted, so a sweep that stops reaching a lane or a flag fails.
+// `staged_bytes`, the bytes each image's stage (rt_trace.hpp LaneImage, which
+// takes its offsets from lane_lds_layout) writes into a region. A sweep of
+// synthetic scenes (the pointers are dummies, never dereferenced) on both sides
+// of every threshold; the outcomes are counted, so a sweep that stops reaching
+// a lane or a flag fails.
 #include <cstdio>
 
 #include "rt_wf_plan.hpp"
@@ -104,46 +105,33 @@ static size_t static_lds(int lane) {
 }
 }  // namespace old
 
-// ---- the bytes lane_scene<LANE> touches, as its text walks them: [begin, end) per region
-// (-1: not staged). The 16-bit stacks: entry k of lane t at halfword k * kTraceBlock + t.
-struct Walk {
-  long stack[2], nodes[2], sph48[2], sph[2], deltas[2], treelet[2];
+// ---- the bytes each LaneImage<LANE>::stage (rt_trace.hpp) writes into a region, or the stack's
+// walks touch: the regions start at the layout's offsets by construction (stage takes them from
+// lane_lds_layout), so what is left to hold is that each ends at or before the next one's offset.
+// (-1: not staged. The 16-bit stacks: entry k of lane t at halfword k * kTraceBlock + t.)
+struct Staged {
+  long stack = -1, nodes = -1, sph48 = -1, sph = -1, deltas = -1, treelet = -1;
 };
-static Walk kernel_walk(int LANE, const DevScene& sc, unsigned lds_flags, unsigned n_top) {
-  Walk w;
-  for (long* r : {w.stack, w.nodes, w.sph48, w.sph, w.deltas, w.treelet}) r[0] = r[1] = -1;
-  auto set = [](long* r, size_t b, size_t n) { r[0] = (long)b; r[1] = (long)(b + n); };
-  size_t p = 0;
-  auto sph48 = [&] {
-    set(w.sph48, p, (size_t)sc.n_diag * 48 + (size_t)sc.n_diag * 4);  // r[i], i < 3 n_diag (16 B each); mt[k]
-    p += sph48_lds_bytes(sc);
-  };
-  if (LANE == 15) {
-    set(w.stack, 0, (size_t)sc.bvhw_stack * kTraceBlock * 2);
-    p += wide_stack_bytes(sc);
-    set(w.nodes, p, (size_t)sc.n_bvhw * sizeof(BvhWide));
-    p += (size_t)sc.n_bvhw * sizeof(BvhWide);
-    sph48();
+static Staged staged_bytes(int lane, const DevScene& sc, unsigned lds_flags, unsigned n_top) {
+  Staged w;
+  const long sph48 = (long)sc.n_diag * 48 + (long)sc.n_diag * 4;  // stage_sph48: r[i], i < 3 n_diag (16 B each); mt[k]
+  if (lane == kLaneWideLds) {
+    w.stack = (long)sc.bvhw_stack * kTraceBlock * 2;
+    w.nodes = (long)sc.n_bvhw * (long)sizeof(BvhWide);
+    w.sph48 = sph48;
   }
-  if (LANE == 4) {
-    set(w.stack, 0, (size_t)sc.bvhw_stack * kTraceBlock * 2);
-    p += wide_stack_bytes(sc);
-    if (n_top > 0) set(w.treelet, p + ((lds_flags & kLdsDeltas) ? delta_lds_bytes(sc) : 0), (size_t)n_top * sizeof(BvhWide16));
+  if (lane == kLaneWide16) {
+    w.stack = (long)sc.bvhw_stack * kTraceBlock * 2;
+    w.treelet = (long)n_top * (long)sizeof(BvhWide16);
   }
-  if (LANE == 14) {
-    set(w.stack, 0, (size_t)(sc.bvh_depth + 1) * kTraceBlock * 2);
-    p += (lane_stack_bytes(sc.bvh_depth + 1) / 2 + 15) & ~(size_t)15;
-    set(w.nodes, p, (size_t)sc.n_bvh * sizeof(BvhPair));
-    p += (size_t)sc.n_bvh * sizeof(BvhPair);
-    sph48();
+  if (lane == kLanePair) {
+    w.stack = (long)(sc.bvh_depth + 1) * kTraceBlock * 2;
+    w.nodes = (long)sc.n_bvh * (long)sizeof(BvhPair);
+    w.sph48 = sph48;
   }
-  if (LANE == 0 && (lds_flags & kLdsSpheres)) {
-    set(w.sph, p, (size_t)sc.n_diag * sizeof(SphereDiag));
-    p += sph_lds_bytes(sc);
-  }
-  if (LANE == 3 && n_top > 0)
-    set(w.treelet, p + ((lds_flags & kLdsDeltas) ? delta_lds_bytes(sc) : 0), (size_t)n_top * sizeof(BvhNode));
-  if (lds_flags & kLdsDeltas) set(w.deltas, p, (size_t)sc.n_lights * sc.n_diag * 2);
+  if (lane == kLaneWave && (lds_flags & kLdsSpheres)) w.sph = (long)sc.n_diag * (long)sizeof(SphereDiag);
+  if (lane == kLaneLdsStack) w.treelet = (long)n_top * (long)sizeof(BvhNode);
+  if (lds_flags & kLdsDeltas) w.deltas = (long)sc.n_lights * sc.n_diag * 2;  // stage_shared
   return w;
 }
 
@@ -224,11 +212,10 @@ int main() {
       const size_t off[7] = {L.stack, L.nodes, L.sph48, L.sph, L.deltas, L.treelet, L.end};
       bool ok = L.stack == 0;
       for (int r = 0; r < 7; ++r) ok = ok && off[r] % 16 == 0 && (r == 0 || off[r - 1] <= off[r]);
-      // ... and what the kernel walks: each staged region starts at the layout's offset and ends inside it
-      const Walk w = kernel_walk(p.lane, sc, p.lds_flags, p.n_top);
-      const long* reg[6] = {w.stack, w.nodes, w.sph48, w.sph, w.deltas, w.treelet};
-      for (int r = 0; r < 6; ++r)
-        ok = ok && (reg[r][0] < 0 ? true : reg[r][0] == (long)off[r] && reg[r][1] <= (long)off[r + 1]);
+      // ... and what the kernel stages there ends inside each region
+      const Staged w = staged_bytes(p.lane, sc, p.lds_flags, p.n_top);
+      const long reg[6] = {w.stack, w.nodes, w.sph48, w.sph, w.deltas, w.treelet};
+      for (int r = 0; r < 6; ++r) ok = ok && (reg[r] < 0 || (long)off[r] + reg[r] <= (long)off[r + 1]);
       if (!ok) fail("layout regions", sc, tn, primary, use_lb, p, o);
       ++n_lane[p.lane][primary];
       if (p.lane == kLaneWave) ++n_sph[(p.lds_flags & kLdsSpheres) ? 1 : 0];

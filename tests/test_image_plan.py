@@ -4,8 +4,9 @@ header against the HIP headers and run without a device: over a sweep of
 synthetic scenes and knob settings the plan equals the rules launch_fused_q
 stated inline before, the dynamic LDS it asks for is the layout's end and fits
 the limit with the kernel's static LDS, the layout's regions are aligned,
-ordered and hold what lane_scene's pointer walk touches, and the sweep reaches
-every image, flag and treelet outcome."""
+ordered and hold what each image's stage (LaneImage, which takes its offsets
+from the layout) writes into them, and the sweep reaches every image, flag and
+treelet outcome."""
 import os
 import shutil
 import subprocess
