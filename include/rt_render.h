@@ -66,7 +66,10 @@ enum {
   RT_SHAPE_PLANE = 1,    /* geometry/shape/plane.rs:19-64    */
   RT_SHAPE_CUBE = 2,     /* geometry/shape/cube.rs:17-106    */
   RT_SHAPE_CYLINDER = 3, /* geometry/shape/cylinder.rs:12-130 */
-  RT_SHAPE_CONE = 4      /* geometry/shape/cone.rs:12-149    */
+  RT_SHAPE_CONE = 4,     /* geometry/shape/cone.rs:12-149    */
+  /* rt_scene_create_mesh only (their vertices come in rt_triangle_desc): */
+  RT_SHAPE_TRIANGLE = 5,       /* geometry/shape/triangle.rs:24-96         */
+  RT_SHAPE_SMOOTH_TRIANGLE = 6 /* geometry/shape/smooth_triangle.rs:27-106 */
 };
 
 /* Anti-aliasing sample counts of `RenderOpts::aa_samples` (camera.rs:221-233). */
@@ -123,6 +126,16 @@ typedef struct rt_group_desc {
   int32_t _pad;
 } rt_group_desc;
 
+/* The vertices of a `Triangle` (triangle.rs:24-44) or `SmoothTriangle`
+ * (smooth_triangle.rs:27-55) in object space; its rt_shape_desc carries the
+ * transform and the material. The library derives e1 = p2 - p1, e2 = p3 - p1
+ * and normal = normalize(cross(e2, e1)) as the constructors do. n1..n3 are
+ * read for RT_SHAPE_SMOOTH_TRIANGLE only. */
+typedef struct rt_triangle_desc {
+  double p1[3], p2[3], p3[3];
+  double n1[3], n2[3], n3[3];
+} rt_triangle_desc;
+
 /* `PointLight` (light.rs:4-24), in `World::lights` insertion order. */
 typedef struct rt_light_desc {
   double position[3];
@@ -158,7 +171,7 @@ typedef struct rt_stats {
   uint64_t sphere_tests;
   uint64_t plane_tests;
   uint64_t sphere_disc_ge0;
-  uint64_t other_tests; /* Cube / Cylinder / Cone local_intersect calls */
+  uint64_t other_tests; /* Cube / Cylinder / Cone / Triangle / SmoothTriangle local_intersect calls */
   double ms_kernel; /* device time of the render kernel(s), HIP events */
   double ms_total;  /* wall time of the call */
   /* ABI 3 */
@@ -212,6 +225,17 @@ int rt_scene_create_groups(const rt_shape_desc* shapes, size_t n_shapes,
                            const int32_t* shape_group, const rt_group_desc* groups,
                            size_t n_groups, const rt_light_desc* lights,
                            size_t n_lights, int device, rt_scene** out);
+/* rt_scene_create_groups for a World with triangles (obj_parser/mod.rs builds
+ * them into groups): the j-th shape whose kind is RT_SHAPE_TRIANGLE or
+ * RT_SHAPE_SMOOTH_TRIANGLE takes tris[j]; `n_tris` must be the number of
+ * such shapes (RT_ERR_INVALID_ARGUMENT otherwise). With n_tris == 0 this is
+ * rt_scene_create_groups. Two triangles are structurally equal only when
+ * their vertices (and, smooth, their normals) are too. */
+int rt_scene_create_mesh(const rt_shape_desc* shapes, size_t n_shapes,
+                         const int32_t* shape_group, const rt_group_desc* groups,
+                         size_t n_groups, const rt_triangle_desc* tris, size_t n_tris,
+                         const rt_light_desc* lights, size_t n_lights, int device,
+                         rt_scene** out);
 void rt_scene_destroy(rt_scene* scene);
 
 /* ---- render entry points -------------------------------------------------- */

@@ -154,6 +154,9 @@ struct Shape {
   double maximum = std::numeric_limits<double>::infinity();
   bool closed = false;
   BoundingBox bbox = BoundingBox(Point(-1, -1, -1), Point(1, 1, 1));  // sphere.rs:20 / cube.rs:22
+  // Triangle / SmoothTriangle (triangle.rs:13-21, smooth_triangle.rs:13-24); n1..n3 of the smooth kind
+  Point p1, p2, p3;
+  Vector n1, n2, n3, e1, e2, normal;
   void set_transform(const Matrix& t) {  // geometry/mod.rs:74-85
     bbox = bbox.transform(transform_inverse);
     const Matrix inv = t.inverse();
@@ -203,6 +206,36 @@ inline Shape Cone(double minimum = -std::numeric_limits<double>::infinity(),
   const double a = std::fabs(minimum), b = std::fabs(maximum), limit = std::fmax(a, b);  // f64::max (cone.rs:29-31)
   s.bbox = BoundingBox(Point(-limit, minimum, -limit), Point(limit, maximum, limit));
   return s;
+}
+// triangle.rs:24-44: the box holds the three points
+inline Shape Triangle(const Point& p1, const Point& p2, const Point& p3) {
+  Shape s;
+  s.kind = RT_SHAPE_TRIANGLE;
+  s.bbox = BoundingBox();
+  s.bbox.add_point(p1);
+  s.bbox.add_point(p2);
+  s.bbox.add_point(p3);
+  s.p1 = p1; s.p2 = p2; s.p3 = p3;
+  s.e1 = p2 - p1;
+  s.e2 = p3 - p1;
+  s.normal = cross(s.e2, s.e1).normalize();
+  return s;
+}
+// smooth_triangle.rs:27-55
+inline Shape SmoothTriangle(const Point& p1, const Point& p2, const Point& p3, const Vector& n1, const Vector& n2,
+                            const Vector& n3) {
+  Shape s = Triangle(p1, p2, p3);
+  s.kind = RT_SHAPE_SMOOTH_TRIANGLE;
+  s.n1 = n1; s.n2 = n2; s.n3 = n3;
+  return s;
+}
+inline rt_triangle_desc to_triangle_desc(const Shape& s) {
+  rt_triangle_desc t;
+  const double v[18] = {s.p1.x, s.p1.y, s.p1.z, s.p2.x, s.p2.y, s.p2.z, s.p3.x, s.p3.y, s.p3.z,
+                        s.n1.x, s.n1.y, s.n1.z, s.n2.x, s.n2.y, s.n2.z, s.n3.x, s.n3.y, s.n3.z};
+  static_assert(sizeof t == sizeof v, "rt_triangle_desc is 18 doubles");
+  std::memcpy(&t, v, sizeof t);
+  return t;
 }
 
 // geometry/shape/group.rs:13-198: a Group holds shapes and groups in order. Its
@@ -446,14 +479,16 @@ class World {
     return *objects_[i].shape;
   }
   PointLight& light(size_t i) { drop(); return lights_.at(i); }
-  // The flattened World (rt_scene_create_groups): the primitives in the order
+  // The flattened World (rt_scene_create_mesh): the primitives in the order
   // World::intersect's flat_map reaches them (group.rs:49-58: each group's
   // children in order), the innermost group of each (-1: none), and the groups
-  // (their boxes, parents first).
+  // (their boxes, parents first); the vertices of the triangles among the
+  // primitives, in their order.
   struct Flat {
     std::vector<rt_shape_desc> shapes;
     std::vector<int32_t> shape_group;
     std::vector<rt_group_desc> groups;
+    std::vector<rt_triangle_desc> tris;
   };
   Flat flatten() const {
     Flat f;
@@ -463,6 +498,7 @@ class World {
         if (c.shape) {
           f.shapes.push_back(to_desc(*c.shape));
           f.shape_group.push_back(parent);
+          if (c.shape->kind >= RT_SHAPE_TRIANGLE) f.tris.push_back(to_triangle_desc(*c.shape));
           return;
         }
         rt_group_desc g;
@@ -502,8 +538,9 @@ class World {
       const Flat f = flatten();
       auto l = light_descs();
       rt_scene* s = nullptr;
-      check(rt_scene_create_groups(f.shapes.data(), f.shapes.size(), f.shape_group.data(), f.groups.data(),
-                                   f.groups.size(), l.data(), l.size(), device, &s), "rt_scene_create");
+      check(rt_scene_create_mesh(f.shapes.data(), f.shapes.size(), f.shape_group.data(), f.groups.data(),
+                                 f.groups.size(), f.tris.data(), f.tris.size(), l.data(), l.size(), device, &s),
+            "rt_scene_create");
       scene_ = s;
       scene_device_ = device;
     }

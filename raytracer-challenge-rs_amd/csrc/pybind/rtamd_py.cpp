@@ -11,6 +11,7 @@
 #include <cstring>
 #include <thread>
 
+#include "../host/obj_parser.hpp"
 #include "../host/rt_world.hpp"
 #include "../host/scene_parser.hpp"
 
@@ -85,7 +86,7 @@ extern "C" int rtamd_nccl_gather_f64(const double* send, double* recv, size_t co
 extern "C" int rtamd_nccl_comm_destroy(void* comm);
 extern "C" int rtamd_wf_profile(const rt_scene* s, int enable, double out[40]);
 extern "C" int rtamd_wf_gen_counts(const rt_scene* s, unsigned* out, int max);
-extern "C" int rtamd_wf_plan(const rt_scene* s, long long out[8]);
+extern "C" int rtamd_wf_plan(const rt_scene* s, long long out[12]);
 extern "C" int rtamd_scene_tuning_set(const rt_scene* s, const char* key, int value);
 extern "C" int rtamd_render_shard_host(const rt_scene* scene, const rt_camera_desc* camera, uint32_t max_depth,
                                        uint32_t aa_samples, uint32_t row_block, uint32_t shard, uint32_t n_shards,
@@ -244,6 +245,10 @@ PYBIND11_MODULE(_rtamd, m) {
       .def("has_shadow", &Shape::has_shadow)
       .def("get_bounds", [](const Shape& s) { return s.bbox; })
       .def("parent_space_bounds", &Shape::parent_space_bounds)
+      // Triangle / SmoothTriangle (zero vectors on the other kinds)
+      .def_readonly("p1", &Shape::p1).def_readonly("p2", &Shape::p2).def_readonly("p3", &Shape::p3)
+      .def_readonly("n1", &Shape::n1).def_readonly("n2", &Shape::n2).def_readonly("n3", &Shape::n3)
+      .def_readonly("e1", &Shape::e1).def_readonly("e2", &Shape::e2).def_readonly("normal", &Shape::normal)
       .def("desc_bytes", [](const Shape& s) { rt_shape_desc d = to_desc(s); return pod_bytes(&d, sizeof d); });
   // geometry/shape/group.rs: children by value (a copy of the shape or group is moved in, as
   // add_child takes its Box); child(i) returns a copy of child i
@@ -284,6 +289,22 @@ PYBIND11_MODULE(_rtamd, m) {
   m.def("Cube", &Cube);
   m.def("Cylinder", &Cylinder, py::arg("minimum") = -std::numeric_limits<double>::infinity(),
         py::arg("maximum") = std::numeric_limits<double>::infinity(), py::arg("closed") = false);
+  m.def("Triangle", &Triangle, py::arg("p1"), py::arg("p2"), py::arg("p3"));
+  m.def("SmoothTriangle", &SmoothTriangle, py::arg("p1"), py::arg("p2"), py::arg("p3"), py::arg("n1"), py::arg("n2"),
+        py::arg("n3"));
+  // obj_parser/mod.rs (host/obj_parser.hpp)
+  py::class_<ObjParser>(m, "ObjParser")
+      .def(py::init<>())
+      .def("parse", &ObjParser::parse)
+      .def("parse_line", &ObjParser::parse_line)
+      .def_readonly("ignored", &ObjParser::ignored)
+      .def_readonly("vertices", &ObjParser::vertices)
+      .def_readonly("normals", &ObjParser::normals)
+      .def("group", [](const ObjParser& p, const std::string& name) { return p.group(name); })  // a copy
+      .def("group_names", &ObjParser::group_names)
+      .def("as_group", &ObjParser::as_group);
+  m.def("parse_obj_file", &parse_obj_file, py::arg("path"));
+  m.def("parse_obj_string", &parse_obj_string, py::arg("text"));
   m.def("Cone", &Cone, py::arg("minimum") = -std::numeric_limits<double>::infinity(),
         py::arg("maximum") = std::numeric_limits<double>::infinity(), py::arg("closed") = false);
 
@@ -384,6 +405,10 @@ PYBIND11_MODULE(_rtamd, m) {
         return pod_bytes(f.groups.data(), f.groups.size() * sizeof(rt_group_desc));
       })
       .def("shape_groups", [](const World& w) { return w.flatten().shape_group; })  // innermost group per shape
+      .def("triangles_bytes", [](const World& w) {  // rt_triangle_desc[], the triangles among the shapes in order
+        const auto t = w.flatten().tris;
+        return pod_bytes(t.data(), t.size() * sizeof(rt_triangle_desc));
+      })
       .def("lights_bytes", [](const World& w) {
         auto l = w.light_descs();
         return pod_bytes(l.data(), l.size() * sizeof(rt_light_desc));
@@ -657,7 +682,7 @@ PYBIND11_MODULE(_rtamd, m) {
   // the image plans of the last render's fused launches (rt_wf_plan.hpp): generation 0's and the
   // last deeper generation's; lane -1 = none. lds_spheres / lds_deltas: the kLdsSpheres / kLdsDeltas flags
   m.def("_wf_plan", [](const World& w) {
-    long long o[8] = {0};
+    long long o[12] = {0};
     check(rtamd_wf_plan(w.scene(), o), "wf_plan");
     py::dict d;
     const char* which[2] = {"primary", "secondary"};
@@ -671,6 +696,9 @@ PYBIND11_MODULE(_rtamd, m) {
       p["dyn"] = o[4 * i + 3];
       d[which[i]] = p;
     }
+    py::dict t;  // the triangle hierarchy (tri_trace): `ran` = the last render walked it
+    t["records"] = o[8]; t["depth"] = o[9]; t["nodes"] = o[10]; t["ran"] = o[11] != 0;
+    d["triangles"] = t;
     return d;
   }, py::arg("world"));
   m.def("_tuning_set", [](const std::string& k, int v) { check(rtamd_tuning_set(k.c_str(), v), "tuning"); });

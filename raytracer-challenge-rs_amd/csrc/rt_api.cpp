@@ -120,7 +120,9 @@ int rtamd_wf_profile(const rt_scene* cs, int enable, double out[40]) {
 // Development hook (not in the public ABI): the image plans (rt_wf_plan.hpp) of the scene's last
 // render's fused launches. out[0..3]: generation 0's lane, lds_flags, n_top, dyn; out[4..7]: the
 // last deeper generation's. Lane -1 (and zeros): no such launch, or the render was not fused.
-int rtamd_wf_plan(const rt_scene* cs, long long out[8]) {
+// out[8..11]: the triangle hierarchy (tri_trace): its records, depth and nodes, and whether the
+// last render walked it (a fused render of a scene that has one).
+int rtamd_wf_plan(const rt_scene* cs, long long out[12]) {
   if (!cs || !out) return fail(RT_ERR_INVALID_ARGUMENT, "null scene or output");
   rt_scene* s = const_cast<rt_scene*>(cs);
   std::lock_guard<std::mutex> lk(s->mu);
@@ -133,6 +135,10 @@ int rtamd_wf_plan(const rt_scene* cs, long long out[8]) {
     out[4 * i + 2] = (long long)pl[i]->n_top;
     out[4 * i + 3] = (long long)pl[i]->dyn;
   }
+  out[8] = s->dev.n_tbvh > 0 ? s->dev.n_trec : 0;
+  out[9] = s->dev.tbvh_depth;
+  out[10] = s->dev.n_tbvh;
+  out[11] = s->dev.n_tbvh > 0 && (pl[0]->lane >= 0 || pl[1]->lane >= 0) ? 1 : 0;
   return RT_OK;
 }
 

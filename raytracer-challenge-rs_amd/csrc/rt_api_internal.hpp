@@ -345,7 +345,7 @@ int render_banded(rt_scene* s, std::unique_lock<std::mutex>& lk, rt_scene::HostC
                   uint32_t max_depth, uint32_t aa, double* out_rgb, bool host_ready = false);
 // the fast path can serve `s` (a hierarchy to cull with, not switched off)
 inline bool fast_path(const rt_scene* s) {
-  return s->tune.accel != 0 && (s->dev.n_bvh > 0 || s->dev.n_obvh > 0 || s->dev.n_lbvh > 0);
+  return s->tune.accel != 0 && (s->dev.n_bvh > 0 || s->dev.n_obvh > 0 || s->dev.n_lbvh > 0 || s->dev.n_tbvh > 0);
 }
 
 inline PpmHeader ppm_header(uint32_t w, uint32_t h) {  // image/ppm.rs:53-63

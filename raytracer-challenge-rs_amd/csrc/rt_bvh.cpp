@@ -666,6 +666,69 @@ std::vector<BvhNode> build_line_bvh(std::vector<QuadRec>& recs, std::vector<Cone
   return nodes;
 }
 
+// The padded world box of a triangle (DESIGN.md §5.2 "Triangles"): its three
+// vertices mapped through the inverse of the record's 3x3 part, widened per
+// axis by what the reference's own rounding can move its root off the
+// triangle, then by the project's rule (pad_axis). The reference solves
+// (-d, e1, e2) (t, u, v)^T = o - p1 =: s by Cramer's rule (triangle.rs:63-90)
+// and accepts 0 <= u, v and u + v <= 1 as computed: the accepted point
+// Q = p1 + u e1 + v e2 lies on the triangle, and the local ray at the
+// computed t is within eta = 64 ulp * kappa * S of Q, with kappa =
+// |d| |e1| |e2| / EPSILON (the reference rejects |det| < EPSILON) and
+// S = |s| + 2 (|e1| + |e2|). tri_trace walks the hierarchy only for rays with
+// |d|_inf <= kTriDirMax and |o|_inf <= kTriOriginMax, which bounds |d| and |s|
+// in object space through the record's inverse A.
+bool tri_box(const TriRec& r, double lo[3], double hi[3]) {
+  double F[3][3];
+  const double cond = invert3(r.m, F);
+  if (!(cond <= 1e6)) return false;  // too ill-conditioned for the padding argument
+  const double b[3] = {r.m[3], r.m[7], r.m[11]};
+  auto norm2 = [](const double* v) { return std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]); };
+  double a_f = 0.0;  // |A|_F
+  for (int i = 0; i < 3; ++i)
+    for (int j = 0; j < 3; ++j) a_f += r.m[4 * i + j] * r.m[4 * i + j];
+  a_f = std::sqrt(a_f);
+  const double s3 = std::sqrt(3.0);
+  const double d_max = a_f * s3 * kTriDirMax;
+  const double s_max = a_f * s3 * kTriOriginMax + norm2(b) + norm2(r.p1);
+  const double ne1 = norm2(r.e1), ne2 = norm2(r.e2);
+  const double kappa = d_max * ne1 * ne2 / kEpsilon + 1.0;
+  const double eta = 64.0 * 0x1p-53 * kappa * (s_max + 2.0 * (ne1 + ne2));
+  if (!(kappa <= 1e12) || !std::isfinite(eta)) return false;
+  const double q[3][3] = {{r.p1[0], r.p1[1], r.p1[2]},
+                          {r.p1[0] + r.e1[0], r.p1[1] + r.e1[1], r.p1[2] + r.e1[2]},
+                          {r.p1[0] + r.e2[0], r.p1[1] + r.e2[1], r.p1[2] + r.e2[2]}};
+  for (int i = 0; i < 3; ++i) {
+    double mn = INFINITY, mx = -INFINITY, slack = 0.0, f1 = 0.0;
+    for (int k = 0; k < 3; ++k) {
+      double w = 0.0, mag = 0.0;  // world vertex k = F (q_k - b), and the magnitude of its terms
+      for (int j = 0; j < 3; ++j) {
+        w += F[i][j] * (q[k][j] - b[j]);
+        mag += std::fabs(F[i][j]) * (std::fabs(q[k][j]) + std::fabs(b[j]));
+      }
+      mn = std::min(mn, w);
+      mx = std::max(mx, w);
+      slack = std::max(slack, mag);
+    }
+    for (int j = 0; j < 3; ++j) f1 += std::fabs(F[i][j]);
+    // eta in world space, and the rounding of F (cofactors, cond <= 1e6) and of the sums above
+    const double h = f1 * eta * (1.0 + 1e-9) + 4e-9 * slack;
+    if (!std::isfinite(mn) || !std::isfinite(mx) || !std::isfinite(h)) return false;
+    pad_axis(mn - h, mx + h, &lo[i], &hi[i]);
+  }
+  return true;
+}
+
+std::vector<BvhNode> build_tri_bvh(std::vector<TriRec>& recs, int leaf_size, int* depth, double trav_cost) {
+  std::vector<Box> boxes(recs.size());
+  for (size_t i = 0; i < recs.size(); ++i)
+    if (!tri_box(recs[i], boxes[i].lo, boxes[i].hi)) return {};  // the caller passes boxed records only
+  std::vector<int> order;
+  std::vector<BvhNode> nodes = build_over_boxes(boxes, leaf_size, trav_cost, depth, &order);
+  if (!nodes.empty()) apply_order(recs, order);
+  return nodes;
+}
+
 // ------------------------------------------------------------ light buffer
 // See rt_layout.hpp (LbCell) and DESIGN.md "Light buffer" for the argument.
 // Margins: the query (binary32, from the binary64 shadow-ray vector) lands

@@ -62,6 +62,15 @@ bool line_box(const QuadRec& r, double lo[3], double hi[3]);
 std::vector<BvhNode> build_line_bvh(std::vector<QuadRec>& recs, std::vector<ConeCluster>* clusters,
                                     std::vector<int32_t>* members, int* depth = nullptr);
 
+// The triangle hierarchy (rt_trace.hpp tri_trace, DESIGN.md §5.2 "Triangles"):
+// tri_box gives the padded world box of a triangle's three vertices (false
+// for an ill-conditioned transform: the exhaustive loop takes it);
+// build_tri_bvh builds the hierarchy over records that all have one
+// (reordered in place into leaf order); empty when there are none.
+bool tri_box(const TriRec& r, double lo[3], double hi[3]);
+std::vector<BvhNode> build_tri_bvh(std::vector<TriRec>& recs, int leaf_size, int* depth = nullptr,
+                                   double trav_cost = 1.0);
+
 // Light buffer over the shadow-casting records, one cube map of R x R cells
 // per face per light (rt_layout.hpp LbCell; DESIGN.md "Light buffer").
 // Empty (cells.size() == 0) when there are no records, or 65535 or more.

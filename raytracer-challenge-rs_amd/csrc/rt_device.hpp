@@ -56,6 +56,7 @@ typedef const RT_CONST SphereGen* cSphereGen;
 typedef const RT_CONST PlaneRec* cPlaneRec;
 typedef const RT_CONST QuadRec* cQuadRec;
 typedef const RT_CONST GroupRec* cGroupRec;
+typedef const RT_CONST TriRec* cTriRec;
 typedef const RT_CONST ConeCluster* cConeCluster;
 typedef const RT_CONST LightRec* cLightRec;
 
@@ -257,6 +258,58 @@ __device__ __forceinline__ void quad_test(QP q, V3 o, V3 d, Hit& h) {
   if (!SHADOW && (n_neg & 1)) push_container(h, neg_t, k0 + neg_i);
 }
 
+// vector.rs:103-109
+__device__ __forceinline__ V3 vcross(V3 a, V3 b) {
+  return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x);
+}
+// Triangle / SmoothTriangle::local_intersect (triangle.rs:63-90,
+// smooth_triangle.rs:74-101), operation for operation: false = the empty
+// list; otherwise the one intersection's t and its u, v. A NaN u fails
+// RangeInclusive::contains, a NaN v passes both comparisons, as there.
+__device__ __forceinline__ bool tri_local_intersect(V3 p1, V3 e1, V3 e2, V3 o, V3 d, double& t, double& u, double& v) {
+  const V3 dir_cross_e2 = vcross(d, e2);
+  const double det = vdot(e1, dir_cross_e2);
+  if (fabs(det) < kEpsilon) return false;
+  const double f = 1.0 / det;
+  const V3 p1_to_origin = vsub(o, p1);
+  u = f * vdot(p1_to_origin, dir_cross_e2);
+  if (!(0.0 <= u && u <= 1.0)) return false;
+  const V3 origin_cross_e1 = vcross(p1_to_origin, e1);
+  v = f * vdot(d, origin_cross_e1);
+  if (v < 0.0 || (u + v) > 1.0) return false;
+  t = f * vdot(e2, origin_cross_e1);
+  return true;
+}
+// Shape::intersect (geometry/mod.rs:46-49) of one TriRec, folded into `h` as
+// quad_test folds a one-entry list: t >= 0 competes by (t, key) at list
+// position 0; t < 0 is an odd number of negative roots, a container candidate.
+// tri_hit: the record's list is not empty, and its t; tri_fold: that intersection into `h`.
+template <typename TP>  // TP: constant-address (wave-uniform) or generic record pointer
+__device__ __forceinline__ bool tri_hit(TP q, V3 o, V3 d, double& t) {
+  const V3 lo = v3(q->m[0] * o.x + q->m[1] * o.y + q->m[2] * o.z + q->m[3],
+                   q->m[4] * o.x + q->m[5] * o.y + q->m[6] * o.z + q->m[7],
+                   q->m[8] * o.x + q->m[9] * o.y + q->m[10] * o.z + q->m[11]);
+  const V3 ld = v3(q->m[0] * d.x + q->m[1] * d.y + q->m[2] * d.z, q->m[4] * d.x + q->m[5] * d.y + q->m[6] * d.z,
+                   q->m[8] * d.x + q->m[9] * d.y + q->m[10] * d.z);
+  double u, v;
+  return tri_local_intersect(v3(q->p1[0], q->p1[1], q->p1[2]), v3(q->e1[0], q->e1[1], q->e1[2]),
+                             v3(q->e2[0], q->e2[1], q->e2[2]), lo, ld, t, u, v);
+}
+template <bool SHADOW>
+__device__ __forceinline__ void tri_fold(int meta, double t, Hit& h) {
+  const int k0 = (meta >> 1) << kKeyShift;
+  if (t >= 0.0) {
+    if ((!SHADOW || (meta & 1)) && better(t, k0, h.t, h.key)) { h.t = t; h.key = k0; h.hin = 0; }
+  } else if (!SHADOW && t < 0.0) {
+    push_container(h, t, k0);
+  }
+}
+template <bool SHADOW, typename TP>
+__device__ __forceinline__ void tri_test(TP q, V3 o, V3 d, Hit& h) {
+  double t;
+  if (tri_hit(q, o, d, t)) tri_fold<SHADOW>(q->meta, t, h);
+}
+
 // BoundingBox::intersects (bounding_box.rs:95-136) of a Group's box, with the
 // reference's operations: per axis (min - o) / d and (max - o) / d, or, when
 // |d| < EPSILON, the numerators times infinity (0 * inf = NaN), swapped when
@@ -305,7 +358,8 @@ struct GateSkips {
 // them keep the sphere loops' register allocation, hence their occupancy).
 // FAST: the fast path's remainder (the records outside both hierarchies;
 // the other bounded records are traversed by other_trace).
-template <bool SHADOW, bool QUADS = true, bool FAST = false>
+// TRIS: the triangles too (the kernels of scenes without solids never meet one).
+template <bool SHADOW, bool QUADS = true, bool FAST = false, bool TRIS = QUADS>
 __device__ __forceinline__ void trace_rest(const DevScene& sc, V3 o, V3 d, Hit& h, unsigned& n_disc,
                                            GateSkips* skips = nullptr) {
   cSphereGen sg = (cSphereGen)(FAST ? sc.fx_gen : sc.sph_gen);
@@ -344,12 +398,23 @@ __device__ __forceinline__ void trace_rest(const DevScene& sc, V3 o, V3 d, Hit& 
       quad_test<SHADOW>(qr + j, o, d, h);
     }
   }
+  if constexpr (TRIS) {
+    cTriRec tr = (cTriRec)(FAST ? sc.fx_tris : sc.tris);
+    const int n_tris = FAST ? sc.n_fx_tris : sc.n_tris;
+    for (int j = 0; j < n_tris; ++j) {
+      if (tr[j].gate && !group_gate(sc, tr[j].gate, o, d)) {
+        if (skips) ++skips->other;
+        continue;
+      }
+      tri_test<SHADOW>(tr + j, o, d, h);
+    }
+  }
 }
 
 // The group gates trace_rest<.., QUADS, true> meets, without its tests: a counted
 // launch's ray that is answered before trace_rest runs (shadow_trace's `first`)
 // still owes the reference's count of the shapes its groups kept out.
-template <bool QUADS>
+template <bool QUADS, bool TRIS = QUADS>
 __device__ __forceinline__ void count_rest_gates(const DevScene& sc, V3 o, V3 d, GateSkips& sk) {
   if (!sc.n_groups) return;
   cSphereGen sg = (cSphereGen)sc.fx_gen;
@@ -362,6 +427,11 @@ __device__ __forceinline__ void count_rest_gates(const DevScene& sc, V3 o, V3 d,
     cQuadRec qr = (cQuadRec)sc.fx_quads;
     for (int j = 0; j < sc.n_fx_quads; ++j)
       if (qr[j].gate && !group_gate(sc, qr[j].gate, o, d)) ++sk.other;
+  }
+  if constexpr (TRIS) {
+    cTriRec tr = (cTriRec)sc.fx_tris;
+    for (int j = 0; j < sc.n_fx_tris; ++j)
+      if (tr[j].gate && !group_gate(sc, tr[j].gate, o, d)) ++sk.other;
   }
 }
 
@@ -396,13 +466,14 @@ __device__ __forceinline__ void diag_test(cSphereDiag r, V3 o, V3 d, Hit& h, uns
 // Generic exhaustive trace over the scene's records in global memory (scalar
 // loads): the batch entry points (rt_hit_batch, rt_is_shadowed_batch) and
 // the wavefront fallback when the trace image does not fit in LDS.
-template <bool SHADOW>
+// TRIS = false: a scene without solids or triangles (trace_rest).
+template <bool SHADOW, bool TRIS = true>
 __device__ __forceinline__ void trace(const DevScene& sc, V3 o, V3 d, Hit& h, unsigned& n_disc,
                                       GateSkips* skips = nullptr) {
   hit_init(h);
   cSphereDiag sd = (cSphereDiag)sc.sph_diag;
   for (int j = 0; j < sc.n_diag; ++j) diag_test<SHADOW>(sd + j, o, d, h, n_disc);
-  trace_rest<SHADOW>(sc, o, d, h, n_disc, skips);
+  trace_rest<SHADOW, true, false, TRIS>(sc, o, d, h, n_disc, skips);
   hit_finish(h);
 }
 
@@ -438,8 +509,30 @@ __device__ __forceinline__ V3 local_normal_at(const ShadeRec& s, V3 p) {
   }
 }
 
+// Triangle::local_normal_at (triangle.rs:92-94): the stored normal; SmoothTriangle's
+// (smooth_triangle.rs:103-105): n2 * u + n3 * v + n1 * (1 - u - v) with the hit
+// intersection's u and v. `Hit` does not carry them: they are computed again here from
+// the same world ray and the same record values with tri_test's operations, so they
+// are the intersection's own bits (a hit passed every rejection there, so only u and
+// v are taken). Out of line: the kernels keep their registers for the walks.
+__device__ __attribute__((noinline)) V3 tri_local_normal(const TriShade* tsp, const double* m, int kind, V3 o, V3 d) {
+  const TriShade& ts = *tsp;
+  if (kind == 5) return v3(ts.normal[0], ts.normal[1], ts.normal[2]);
+  const V3 lo = m34_point(m, o);
+  const V3 ld = v3(m[0] * d.x + m[1] * d.y + m[2] * d.z, m[4] * d.x + m[5] * d.y + m[6] * d.z,
+                   m[8] * d.x + m[9] * d.y + m[10] * d.z);
+  double t = 0.0, u = 0.0, v = 0.0;
+  (void)tri_local_intersect(v3(ts.p1[0], ts.p1[1], ts.p1[2]), v3(ts.e1[0], ts.e1[1], ts.e1[2]),
+                            v3(ts.e2[0], ts.e2[1], ts.e2[2]), lo, ld, t, u, v);
+  const V3 n1 = v3(ts.n1[0], ts.n1[1], ts.n1[2]), n2 = v3(ts.n2[0], ts.n2[1], ts.n2[2]);
+  const V3 n3 = v3(ts.n3[0], ts.n3[1], ts.n3[2]);
+  return vadd(vadd(vscale(n2, u), vscale(n3, v)), vscale(n1, 1.0 - u - v));
+}
+
 // Intersection::prepare_computations (intersection.rs:53-105) with the exact
 // top-2 replacement of the containers walk.
+// TRIS = false: the kernels of scenes without triangles leave their normals out.
+template <bool TRIS = true>
 __device__ __forceinline__ Comps prepare(const DevScene& sc, V3 o, V3 d, const Hit& h) {
   Comps c;
   const int obj = h.key >> kKeyShift;
@@ -449,7 +542,10 @@ __device__ __forceinline__ Comps prepare(const DevScene& sc, V3 o, V3 d, const H
   c.eyev = vneg(d);
   // Shape::normal_at (geometry/mod.rs:51-56)
   const V3 lp = m34_point(s.inv, c.point);
-  V3 n = vnormalize(m33_vector(s.invT, local_normal_at(s, lp)));
+  V3 ln;
+  if (TRIS && s.kind >= 5) ln = tri_local_normal(sc.tri_shade + (s.pad0 - 1), s.inv, s.kind, o, d);
+  else ln = local_normal_at(s, lp);
+  V3 n = vnormalize(m33_vector(s.invT, ln));
   c.inside = false;
   if (vdot(n, c.eyev) < 0.0) { c.inside = true; n = vneg(n); }
   c.normal = n;

@@ -9,6 +9,8 @@
 //       PlaneRec    8 doubles  (64 B)  inverse row 1 (only y matters)
 //       QuadRec    16 doubles (128 B)  Cube / Cylinder / Cone: inverse rows 0-2,
 //                                      minimum, maximum, kind, closed
+//       TriRec     24 doubles (192 B)  Triangle / SmoothTriangle: inverse rows
+//                                      0-2, p1, e1, e2
 //     each carries `meta` = (object index << 1) | casts_shadow.
 //   shade records  : ShadeRec per object index (AoS, 64 doubles = 512 B),
 //                    gathered per lane only at a hit.
@@ -57,6 +59,32 @@ struct alignas(64) GroupRec {
   int32_t parent, pad0;
   int64_t pad;
 };
+// Triangle / SmoothTriangle (triangle.rs, smooth_triangle.rs): inverse rows
+// 0..2 (a triangle of a transformed group has its group's transform), p1 and
+// the edges e1 = p2 - p1, e2 = p3 - p1 as the constructors derive them.
+// `kind` = RT_SHAPE_TRIANGLE / RT_SHAPE_SMOOTH_TRIANGLE; `tri` = its TriShade.
+struct alignas(64) TriRec {
+  double m[12];
+  double p1[3], e1[3], e2[3];
+  int32_t meta, gate;
+  int32_t kind, tri;
+  int64_t pad;
+};
+static_assert(sizeof(TriRec) == 192, "TriRec must stay 192 B");
+// The rays the triangle hierarchy's padding is sized for (rt_bvh.cpp tri_box,
+// rt_trace.hpp tri_trace): |d|_inf and |o|_inf at most these.
+constexpr double kTriDirMax = 2.0, kTriOriginMax = 16384.0;
+// What a hit on a triangle reads besides its ShadeRec (ShadeRec::pad0 = 1 + its
+// index here, 0 for every other kind): the flat normal, the vertex normals of
+// the smooth kind, and p1 / e1 / e2 again, from which prepare() recomputes the
+// hit's u and v (tri_local_intersect's operations on the same operands).
+struct alignas(64) TriShade {
+  double normal[3];
+  double n1[3], n2[3], n3[3];
+  double p1[3], e1[3], e2[3];
+  double pad[3];
+};
+static_assert(sizeof(TriShade) == 192, "TriShade must stay 192 B");
 static_assert(sizeof(GroupRec) == 64, "GroupRec must stay 64 B");
 static_assert(sizeof(QuadRec) == 128, "QuadRec must stay 128 B");
 
@@ -272,6 +300,16 @@ struct DevScene {
   // Groups (group.rs): the records' gates index this table (rt_scene_create_groups)
   const GroupRec* groups;
   int32_t n_groups, pad_groups;
+  // Triangles (rt_scene_create_mesh): every record in object order (the
+  // exhaustive loops), their shade table, and on the fast path the hierarchy
+  // over them (tri_trace; `trec` in its leaf order) with the records it does
+  // not hold (`fx_tris`, tested exhaustively by trace_rest)
+  const TriRec* tris;
+  const TriShade* tri_shade;
+  const BvhNode* tbvh;  // nullptr when there is none
+  const TriRec* trec;
+  const TriRec* fx_tris;
+  int32_t n_tris, n_tbvh, n_trec, n_fx_tris, tbvh_depth, pad_tris;
 };
 
 constexpr int32_t kOwnOutside = 0x40000000, kOwnIndex = 0x3FFFFFFF;  // DevScene::obj_diag

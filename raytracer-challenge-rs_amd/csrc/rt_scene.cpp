@@ -1,4 +1,4 @@
-// rt_scene.cpp — rt_scene_create / rt_scene_create_groups / rt_scene_destroy:
+// rt_scene.cpp — rt_scene_create / rt_scene_create_groups / rt_scene_create_mesh / rt_scene_destroy:
 // the reference's World (world.rs:18-21, shape/group.rs) flattened into SoA
 // records in the reference's object order, the exact-culling hierarchies
 // (rt_bvh.cpp), the light buffer, and one upload to the scene's device.
@@ -28,8 +28,17 @@ bool c3_eq(const double* a, const double* b) {
 // Pattern, pattern/mod.rs:17). The bounding box is left out, so this is a
 // SUPERSET of the reference relation: "no pair passes" certifies that the
 // containers walk never sees two structurally-equal objects.
-bool may_be_equal(const rt_shape_desc& a, const rt_shape_desc& b) {
+// `ta`, `tb`: the vertices of a Triangle / SmoothTriangle (null for the other kinds): the derived
+// PartialEq compares p1..p3, and n1..n3 of the smooth kind, through Point's and Vector's `equal()`
+// (triangle.rs:12, smooth_triangle.rs:12); e1, e2 and normal follow from the points.
+bool may_be_equal(const rt_shape_desc& a, const rt_shape_desc& b, const rt_triangle_desc* ta = nullptr,
+                  const rt_triangle_desc* tb = nullptr) {
   if (a.kind != b.kind || (a.casts_shadow != 0) != (b.casts_shadow != 0)) return false;
+  if (ta && tb) {  // first: the triangles of a mesh share everything else
+    if (!(c3_eq(ta->p1, tb->p1) && c3_eq(ta->p2, tb->p2) && c3_eq(ta->p3, tb->p3))) return false;
+    if (a.kind == RT_SHAPE_SMOOTH_TRIANGLE && !(c3_eq(ta->n1, tb->n1) && c3_eq(ta->n2, tb->n2) && c3_eq(ta->n3, tb->n3)))
+      return false;
+  }
   if (!m16_eq(a.transform, b.transform) || !m16_eq(a.inverse, b.inverse)) return false;
   if (!c3_eq(a.color, b.color)) return false;
   if (!(a.ambient == b.ambient && a.diffuse == b.diffuse && a.specular == b.specular &&
@@ -50,14 +59,30 @@ bool may_be_equal(const rt_shape_desc& a, const rt_shape_desc& b) {
   return true;
 }
 
-int find_duplicate(const rt_shape_desc* s, size_t n, size_t* ia, size_t* ib) {
+// `tri_of[i]`: shape i's vertices (null: not a triangle; `tri_of` empty: no triangles at all).
+int find_duplicate(const rt_shape_desc* s, size_t n, const std::vector<const rt_triangle_desc*>& tri_of, size_t* ia,
+                   size_t* ib) {
+  // Equal shapes have |translation-x difference| < EPSILON: sweep a sorted key. The triangles of
+  // a mesh share their transform, so their key adds p1: x + c1 y + c2 z with incommensurable
+  // weights keeps the vertices of a regular grid apart; equal triangles' keys differ by less
+  // than (2 + c1 + c2) EPSILON (and the rounding of the key itself, the relative term).
+  constexpr double c1 = 0.7548776662466927, c2 = 0.5698402909980532;
+  const bool tris = !tri_of.empty();
+  std::vector<std::pair<double, size_t>> key(n);  // (key, shape), sorted by value: no indirection in the sort
+  for (size_t i = 0; i < n; ++i) {
+    double k = s[i].transform[3];
+    if (tris && tri_of[i]) k += tri_of[i]->p1[0] + c1 * tri_of[i]->p1[1] + c2 * tri_of[i]->p1[2];
+    key[i] = {std::isfinite(k) ? k : INFINITY, i};  // (a non-finite coordinate equals nothing)
+  }
+  const double window = tris ? (2.0 + c1 + c2) * rt::EPSILON : rt::EPSILON;
+  std::sort(key.begin(), key.end());
   std::vector<size_t> idx(n);
-  for (size_t i = 0; i < n; ++i) idx[i] = i;
-  // equal shapes have |translation-x difference| < EPSILON: sweep a sorted key
-  std::sort(idx.begin(), idx.end(), [&](size_t a, size_t b) { return s[a].transform[3] < s[b].transform[3]; });
+  for (size_t i = 0; i < n; ++i) idx[i] = key[i].second;
   for (size_t p = 0; p < n; ++p)
-    for (size_t q = p + 1; q < n && s[idx[q]].transform[3] - s[idx[p]].transform[3] < rt::EPSILON; ++q)
-      if (may_be_equal(s[idx[p]], s[idx[q]])) {
+    for (size_t q = p + 1;
+         q < n && key[q].first - key[p].first < window + (tris ? 1e-13 * (std::fabs(key[q].first) + std::fabs(key[p].first)) : 0.0);
+         ++q)
+      if (may_be_equal(s[idx[p]], s[idx[q]], tris ? tri_of[idx[p]] : nullptr, tris ? tri_of[idx[q]] : nullptr)) {
         *ia = std::min(idx[p], idx[q]);
         *ib = std::max(idx[p], idx[q]);
         return 1;
@@ -79,8 +104,15 @@ int rt_scene_create(const rt_shape_desc* shapes, size_t n_shapes, const rt_light
 int rt_scene_create_groups(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* shape_group,
                            const rt_group_desc* groups, size_t n_groups, const rt_light_desc* lights,
                            size_t n_lights, int device, rt_scene** out) {
+  return rt_scene_create_mesh(shapes, n_shapes, shape_group, groups, n_groups, nullptr, 0, lights, n_lights, device, out);
+}
+
+int rt_scene_create_mesh(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* shape_group,
+                         const rt_group_desc* groups, size_t n_groups, const rt_triangle_desc* tri_descs, size_t n_tris,
+                         const rt_light_desc* lights, size_t n_lights, int device, rt_scene** out) {
   return guarded([&]() -> int {
-  if (!out || (n_shapes && !shapes) || (n_lights && !lights) || (n_groups && (!groups || !shape_group)))
+  if (!out || (n_shapes && !shapes) || (n_lights && !lights) || (n_groups && (!groups || !shape_group)) ||
+      (n_tris && !tri_descs))
     return fail(RT_ERR_INVALID_ARGUMENT, "null pointer");
   *out = nullptr;
   if (n_shapes > (size_t)(1u << 29)) return fail(RT_ERR_INVALID_ARGUMENT, "too many shapes");
@@ -95,14 +127,30 @@ int rt_scene_create_groups(const rt_shape_desc* shapes, size_t n_shapes, const i
       return fail(RT_ERR_INVALID_ARGUMENT, "shape " + std::to_string(i) + ": bad group index");
   auto gate_of = [&](size_t i) -> int32_t { return shape_group && n_groups ? shape_group[i] + 1 : 0; };
   for (size_t i = 0; i < n_shapes; ++i) {
-    if (shapes[i].kind < RT_SHAPE_SPHERE || shapes[i].kind > RT_SHAPE_CONE)
+    // (without vertex data, rt_scene_create / rt_scene_create_groups: no triangles)
+    if (shapes[i].kind < RT_SHAPE_SPHERE || shapes[i].kind > (n_tris ? RT_SHAPE_SMOOTH_TRIANGLE : RT_SHAPE_CONE))
       return fail(RT_ERR_UNSUPPORTED_SHAPE, "shape " + std::to_string(i) +
-                                                ": supported kinds are Sphere, Plane, Cube, Cylinder, Cone");
+                                                ": supported kinds are Sphere, Plane, Cube, Cylinder, Cone" +
+                                                (n_tris ? ", Triangle, SmoothTriangle" : ""));
     if (shapes[i].pattern_kind < RT_PATTERN_NONE || shapes[i].pattern_kind > RT_PATTERN_CHECKERS)
       return fail(RT_ERR_INVALID_ARGUMENT, "shape " + std::to_string(i) + ": bad pattern kind");
   }
+  // the j-th triangle shape takes tri_descs[j]
+  std::vector<const rt_triangle_desc*> tri_of;
+  if (n_tris) {
+    tri_of.assign(n_shapes, nullptr);
+    size_t j = 0;
+    for (size_t i = 0; i < n_shapes; ++i)
+      if (shapes[i].kind >= RT_SHAPE_TRIANGLE) {
+        if (j < n_tris) tri_of[i] = tri_descs + j;
+        ++j;
+      }
+    if (j != n_tris)
+      return fail(RT_ERR_INVALID_ARGUMENT, "n_tris is " + std::to_string(n_tris) + ", the shapes hold " +
+                                               std::to_string(j) + " triangles");
+  }
   size_t da, db;
-  if (find_duplicate(shapes, n_shapes, &da, &db))
+  if (find_duplicate(shapes, n_shapes, tri_of, &da, &db))
     return fail(RT_ERR_DUPLICATE_SHAPES, "shapes " + std::to_string(da) + " and " + std::to_string(db) +
                                              " may be structurally equal (containers walk, intersection.rs:63-90)");
 
@@ -115,6 +163,8 @@ int rt_scene_create_groups(const rt_shape_desc* shapes, size_t n_shapes, const i
   std::vector<SphereGen> gen;
   std::vector<PlaneRec> planes;
   std::vector<QuadRec> quads;
+  std::vector<TriRec> tris;
+  std::vector<TriShade> tri_shade;
   std::vector<ShadeRec> shade(n_shapes);
   for (size_t i = 0; i < n_shapes; ++i) {
     const rt_shape_desc& d = shapes[i];
@@ -140,6 +190,26 @@ int rt_scene_create_groups(const rt_shape_desc* shapes, size_t n_shapes, const i
       r.meta = meta;
       r.gate = gate;
       planes.push_back(r);
+    } else if (d.kind >= RT_SHAPE_TRIANGLE) {
+      // Triangle::new / SmoothTriangle::new (triangle.rs:24-44, smooth_triangle.rs:27-55)
+      const rt_triangle_desc& t = *tri_of[i];
+      const rt::Point p1(t.p1[0], t.p1[1], t.p1[2]), p2(t.p2[0], t.p2[1], t.p2[2]), p3(t.p3[0], t.p3[1], t.p3[2]);
+      const rt::Vector e1 = p2 - p1, e2 = p3 - p1, normal = rt::cross(e2, e1).normalize();
+      TriRec r{};
+      TriShade ts{};
+      for (int e = 0; e < 12; ++e) r.m[e] = d.inverse[e];
+      const double p[3] = {p1.x, p1.y, p1.z}, a[3] = {e1.x, e1.y, e1.z}, b[3] = {e2.x, e2.y, e2.z};
+      const double nn[3] = {normal.x, normal.y, normal.z};
+      for (int c = 0; c < 3; ++c) {
+        r.p1[c] = ts.p1[c] = p[c]; r.e1[c] = ts.e1[c] = a[c]; r.e2[c] = ts.e2[c] = b[c];
+        ts.normal[c] = nn[c]; ts.n1[c] = t.n1[c]; ts.n2[c] = t.n2[c]; ts.n3[c] = t.n3[c];
+      }
+      r.meta = (int32_t)meta;
+      r.gate = gate;
+      r.kind = d.kind;
+      r.tri = (int32_t)tri_shade.size();
+      tris.push_back(r);
+      tri_shade.push_back(ts);
     } else {
       QuadRec r{};
       for (int e = 0; e < 12; ++e) r.m[e] = d.inverse[e];
@@ -163,6 +233,7 @@ int rt_scene_create_groups(const rt_shape_desc* shapes, size_t n_shapes, const i
     for (int c = 0; c < 3; ++c) { s.pat_a[c] = d.pattern_a[c]; s.pat_b[c] = d.pattern_b[c]; }
     for (int e = 0; e < 12; ++e) s.pat_inv[e] = d.pattern_inverse[e];
     s.kind = d.kind;
+    s.pad0 = d.kind >= RT_SHAPE_TRIANGLE ? (int32_t)tri_shade.size() : 0;  // 1 + its TriShade (pushed above)
     s.shadow = d.casts_shadow ? 1 : 0;
     s.minimum = d.minimum;
     s.maximum = d.maximum;
@@ -234,6 +305,19 @@ int rt_scene_create_groups(const rt_shape_desc* shapes, size_t n_shapes, const i
     lclus.clear();
     lcone.clear();
   }
+  // ... and over the triangles (tri_trace: grouped ones too, their gate at the leaf); those
+  // without a box (an ill-conditioned inverse), or all of them below the threshold, stay exhaustive
+  std::vector<TriRec> trec, fx_tris;
+  for (const TriRec& r : tris) (tri_box(r, blo, bhi) ? trec : fx_tris).push_back(r);
+  int tbvh_depth = 0;
+  std::vector<BvhNode> tbvh;
+  if (trec.size() >= kMinHierRecords || (bvh.empty() && obvh.empty() && lbvh.empty() && !trec.empty()))
+    tbvh = build_tri_bvh(trec, leaf, &tbvh_depth, g_bvh_ct / 100.0);
+  if (tbvh.empty() || tbvh_depth > kBvhMaxDepth) {  // none, or deeper than tri_trace's stack: exhaustive
+    fx_tris = tris;
+    trec.clear();
+    tbvh.clear();
+  }
   std::vector<int32_t> lrec_clus(line_rec.size(), -1);  // each cone's cluster (line_trace's pre-pass check)
   for (size_t c = 0; c < lclus.size(); ++c)
     for (int32_t j = lclus[c].first; j < lclus[c].first + lclus[c].count; ++j) lrec_clus[(size_t)lcone[(size_t)j]] = (int32_t)c;
@@ -289,7 +373,12 @@ int rt_scene_create_groups(const rt_shape_desc* shapes, size_t n_shapes, const i
   const size_t o_ld = align(o_lv + (lb.ov.size() + 1) * sizeof(uint16_t));
   const size_t o_ll = align(o_ld + lb.delta.size() * sizeof(float));
   const size_t o_gr = align(o_ll + lb.limit.size() * sizeof(float));
-  const size_t total = align(o_gr + grec.size() * sizeof(GroupRec)) + 256;
+  const size_t o_tr = align(o_gr + grec.size() * sizeof(GroupRec));
+  const size_t o_ts = align(o_tr + (tris.size() + 1) * sizeof(TriRec));
+  const size_t o_tb = align(o_ts + (tri_shade.size() + 1) * sizeof(TriShade));
+  const size_t o_tl = align(o_tb + (tbvh.size() + 1) * sizeof(BvhNode));
+  const size_t o_tx = align(o_tl + (trec.size() + 1) * sizeof(TriRec));
+  const size_t total = align(o_tx + (fx_tris.size() + 1) * sizeof(TriRec)) + 256;
   std::vector<unsigned char> host(total, 0);
   if (!diag.empty()) std::memcpy(&host[o_diag], diag.data(), diag.size() * sizeof(SphereDiag));
   if (!gen.empty()) std::memcpy(&host[o_gen], gen.data(), gen.size() * sizeof(SphereGen));
@@ -333,6 +422,11 @@ int rt_scene_create_groups(const rt_shape_desc* shapes, size_t n_shapes, const i
   }
   if (!lrec.empty()) std::memcpy(&host[o_li], lrec.data(), lrec.size() * sizeof(LightRec));
   if (!grec.empty()) std::memcpy(&host[o_gr], grec.data(), grec.size() * sizeof(GroupRec));
+  if (!tris.empty()) std::memcpy(&host[o_tr], tris.data(), tris.size() * sizeof(TriRec));
+  if (!tri_shade.empty()) std::memcpy(&host[o_ts], tri_shade.data(), tri_shade.size() * sizeof(TriShade));
+  if (!tbvh.empty()) std::memcpy(&host[o_tb], tbvh.data(), tbvh.size() * sizeof(BvhNode));
+  if (!trec.empty()) std::memcpy(&host[o_tl], trec.data(), trec.size() * sizeof(TriRec));
+  if (!fx_tris.empty()) std::memcpy(&host[o_tx], fx_tris.data(), fx_tris.size() * sizeof(TriRec));
   if (!lb.cells.empty()) {
     std::memcpy(&host[o_lc], lb.cells.data(), lb.cells.size() * sizeof(LbCell));
     if (!lb.ov.empty()) std::memcpy(&host[o_lv], lb.ov.data(), lb.ov.size() * sizeof(uint16_t));
@@ -408,6 +502,16 @@ int rt_scene_create_groups(const rt_shape_desc* shapes, size_t n_shapes, const i
   s->dev.lights = (const LightRec*)(b + o_li);
   s->dev.groups = (const GroupRec*)(b + o_gr);
   s->dev.n_groups = (int32_t)n_groups;
+  s->dev.tris = (const TriRec*)(b + o_tr);
+  s->dev.tri_shade = (const TriShade*)(b + o_ts);
+  s->dev.tbvh = tbvh.empty() ? nullptr : (const BvhNode*)(b + o_tb);
+  s->dev.trec = (const TriRec*)(b + o_tl);
+  s->dev.fx_tris = (const TriRec*)(b + o_tx);
+  s->dev.n_tris = (int32_t)tris.size();
+  s->dev.n_tbvh = (int32_t)tbvh.size();
+  s->dev.n_trec = (int32_t)trec.size();
+  s->dev.n_fx_tris = (int32_t)fx_tris.size();
+  s->dev.tbvh_depth = tbvh_depth;
   s->dev.n_diag = (int32_t)diag.size();
   s->dev.n_gen = (int32_t)gen.size();
   s->dev.n_planes = (int32_t)planes.size();

@@ -727,11 +727,80 @@ __device__ __forceinline__ void line_trace(const DevScene& sc, V3 o, V3 d, doubl
     e = nn > 0 ? next[0] : (sp > 0 ? stk[--sp] : kBvhEmpty);
   }
 }
+// The triangle hierarchy (DESIGN.md §5.2 "Triangles"): a triangle is an open
+// surface, so one behind the origin (t < 0) enters `containers` although the
+// ray's [0, t_hi] never meets its box. The line hierarchy's rule therefore: a
+// child is entered when its box meets the ray's line within (-inf, t_hi]
+// (radiance rays) or [0, distance) (shadow rays: only those roots block). The
+// one root of a triangle lies on the triangle, inside its padded box. Unlike
+// the line hierarchy this one holds grouped records (every triangle of an OBJ
+// file sits in a group): the gate is tested at the leaf, as other_test does, but
+// only once the triangle's own test has found a root: the two answers are
+// independent, most leaf tests find none, and a gate is a chain of box tests
+// with divisions (a divided 8 192-triangle torus: 49 -> 27 ms per frame,
+// profiles/mesh_ab.txt). Order-independent minima, so the visiting order is free.
+// The boxes' padding (rt_bvh.cpp tri_box) covers the rounding of the reference's
+// own u, v and t for rays with |d|_inf <= kTriDirMax from origins with |o|_inf <=
+// kTriOriginMax (every ray the pipeline makes itself is a unit vector); any
+// other ray (a caller's, a NaN) tests every record of the hierarchy.
+template <bool SHADOW>
+__device__ __forceinline__ void tri_trace(const DevScene& sc, V3 o, V3 d, double t_shadow, Hit& h,
+                                          unsigned& n_tests, unsigned& n_boxes) {
+  if (sc.n_tbvh == 0 || (SHADOW && h.key >= 0 && h.t < t_shadow)) return;
+  const double dm = fmax(fmax(fabs(d.x), fabs(d.y)), fabs(d.z)), om = fmax(fmax(fabs(o.x), fabs(o.y)), fabs(o.z));
+  if (!(dm <= kTriDirMax && om <= kTriOriginMax) || d.x != d.x || d.y != d.y || d.z != d.z || o.x != o.x ||
+      o.y != o.y || o.z != o.z) {
+    for (int k = 0; k < sc.n_trec; ++k) {
+      const TriRec* q = sc.trec + k;
+      double t;
+      ++n_tests;
+      if (tri_hit(q, o, d, t) && (!q->gate || group_gate(sc, q->gate, o, d))) tri_fold<SHADOW>(q->meta, t, h);
+    }
+    return;
+  }
+  const BvhNode* nodes = sc.tbvh;
+  float M[3];
+  root_bound(nodes, M);
+  const SlabRay sr = slab_ray(o, d, M);
+  const float t_lo = SHADOW ? 0.0f : -INFINITY;
+  float t_hi = f32_up(SHADOW ? t_shadow : h.t);
+  int stk[kBvhMaxDepth + 4];
+  int sp = 0, e = 0;
+  while (e != kBvhEmpty) {
+    const BvhNode& nd = nodes[e];
+    int next[2], nn = 0;
+    for (int c = 0; c < 2; ++c) {
+      const int32_t code = nd.child[c];
+      if (code == kBvhEmpty) continue;
+      ++n_boxes;
+      float t_in;
+      if (!slab_hit32(nd.lo[c], nd.hi[c], sr, t_hi, t_in, t_lo)) continue;
+      if (code >= 0) { next[nn++] = code; continue; }
+      const int lc = -(code + 1), first = lc >> 7, cnt = lc & 127;
+      for (int k = first; k < first + cnt; ++k) {
+        const TriRec* q = sc.trec + k;
+        double t;
+        ++n_tests;
+        // (the gate: Group::intersect, group.rs:49-58)
+        if (!(tri_hit(q, o, d, t) && (!q->gate || group_gate(sc, q->gate, o, d)))) continue;
+        tri_fold<SHADOW>(q->meta, t, h);
+        if constexpr (SHADOW) {
+          if (h.key >= 0 && h.t < t_shadow) return;  // shadowed: done
+        } else {
+          t_hi = f32_up(h.t);
+        }
+      }
+    }
+    if (nn == 2) stk[sp++] = next[1];
+    e = nn > 0 ? next[0] : (sp > 0 ? stk[--sp] : kBvhEmpty);
+  }
+}
 // Counted launches (the reference's shape tests come from the group gates
 // each ray met, GateSkips): the gates of the grouped records the other
-// records' hierarchy holds (trace_rest counts those of the records it loops
-// over; the line hierarchy holds no grouped record). Every record is visited
-// here, so only counted launches call it.
+// records' and the triangles' hierarchies hold (trace_rest counts those of the
+// records it loops over; the line hierarchy holds no grouped record). Every
+// record is visited here, so only counted launches call it.
+template <bool TRIS>
 __device__ __forceinline__ void count_hier_gates(const DevScene& sc, V3 o, V3 d, GateSkips& sk) {
   if (!sc.n_groups) return;
   const cQuadRec orec = (cQuadRec)sc.orec;
@@ -739,6 +808,13 @@ __device__ __forceinline__ void count_hier_gates(const DevScene& sc, V3 o, V3 d,
     const int g = orec[k].gate;
     if (g && !group_gate(sc, g, o, d)) {
       if (orec[k].kind == 0) ++sk.sph; else ++sk.other;
+    }
+  }
+  if constexpr (TRIS) {
+    const cTriRec trec = (cTriRec)sc.trec;
+    for (int k = 0; k < sc.n_trec; ++k) {
+      const int g = trec[k].gate;
+      if (g && !group_gate(sc, g, o, d)) ++sk.other;
     }
   }
 }
@@ -1029,7 +1105,8 @@ __device__ __forceinline__ void lb_walk(const DevScene& sc, SD sd, const float* 
 // TALLY (a counted launch): a ray that `first` answers still counts the group
 // gates of the records it did not get to (count_rest_gates; the caller counts
 // the other hierarchy's, count_hier_gates).
-template <bool QUADS, bool TALLY = false, typename Image>
+// TRIS: the scene has triangles (trace_rest's loop over those outside the hierarchy, tri_trace).
+template <bool QUADS, bool TALLY = false, bool TRIS = false, typename Image>
 __device__ __forceinline__ bool shadow_trace(const DevScene& sc, unsigned use_lb, const Image& img, unsigned l,
                                              V3 o, V3 d, double dist, unsigned& n_disc, unsigned& n_tests,
                                              unsigned& n_boxes, GateSkips* skips = nullptr, int first = -1,
@@ -1041,16 +1118,17 @@ __device__ __forceinline__ bool shadow_trace(const DevScene& sc, unsigned use_lb
     ++n_tests;
     if (h.key >= 0 && h.t < dist) {
       if constexpr (TALLY) {
-        if (skips) count_rest_gates<QUADS>(sc, o, d, *skips);
+        if (skips) count_rest_gates<QUADS, TRIS>(sc, o, d, *skips);
       }
       return true;
     }
   }
-  trace_rest<true, QUADS, true>(sc, o, d, h, n_disc, skips);
+  trace_rest<true, QUADS, true, TRIS>(sc, o, d, h, n_disc, skips);
   if constexpr (QUADS) {
     other_trace<true>(sc, o, d, dist, h, n_disc, n_tests, n_boxes);
     line_trace<true>(sc, o, d, dist, h, n_tests, n_boxes);
   }
+  if constexpr (TRIS) tri_trace<true>(sc, o, d, dist, h, n_tests, n_boxes);
   if (!(h.key >= 0 && h.t < dist)) {
     if (use_lb) lb_walk(sc, img.sd, img.delta, img.delta16, l, o, d, dist, h, n_disc, n_tests, skip);
     else img.template walk<true>(sc, o, d, dist, h, n_disc, n_tests, n_boxes);

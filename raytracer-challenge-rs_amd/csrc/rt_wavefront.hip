@@ -349,7 +349,7 @@ static hipError_t launch_shadow_exh(const DevScene& sc, const WfArgs& a, bool ld
 // ---- the fast path: one fused launch per generation over the image wf_plan_image chooses
 // (rt_wf_plan.hpp); `ran` receives the plan. The global-memory images' launches live in their
 // own code object (rt_wavefront_glb.o).
-template <bool QUADS, bool TALLY>
+template <bool QUADS, bool TALLY, bool TRIS = false>
 static hipError_t launch_fused_q(const DevScene& sc, const DevCamera& cam, WfArgs a, bool primary, unsigned n,
                                  hipStream_t stream, const WfTuning& tn, WfImagePlan* ran) {
   // (spread: the whole grid, whatever n; the kernel deals the chunks over every block)
@@ -359,7 +359,7 @@ static hipError_t launch_fused_q(const DevScene& sc, const DevCamera& cam, WfArg
   a.lds_flags = plan.lds_flags;
   a.n_top = plan.n_top;
   const bool cam_rays = a.g == 0 && a.camera_mode;  // only generation 0 of a camera render reads camera rays
-#define RT_LDS(P, L, C) launch_timed(wf_trace_fused<P, QUADS, L, TALLY, C>, tb, plan.dyn, n, stream, sc, cam, a)
+#define RT_LDS(P, L, C) launch_timed(wf_trace_fused<P, QUADS, L, TALLY, C, TRIS>, tb, plan.dyn, n, stream, sc, cam, a)
   switch (plan.lane) {
     case kLaneWave: return RT_LDS(true, kLaneWave, true);
     case kLaneWideLds: return cam_rays ? RT_LDS(false, kLaneWideLds, true) : RT_LDS(false, kLaneWideLds, false);
@@ -367,12 +367,15 @@ static hipError_t launch_fused_q(const DevScene& sc, const DevCamera& cam, WfArg
   }
 #undef RT_LDS
   if (t_ev_start) ++t_ev_used;
-  return wf_launch_global(plan.lane, QUADS, TALLY, cam_rays, sc, cam, a, plan.dyn, n, stream, tb, t_ev_start, t_ev_stop);
+  return wf_launch_global(plan.lane, QUADS, TRIS, TALLY, cam_rays, sc, cam, a, plan.dyn, n, stream, tb, t_ev_start, t_ev_stop);
 }
 static hipError_t launch_fused(const DevScene& sc, const DevCamera& cam, const WfArgs& a, bool primary, unsigned n,
                                hipStream_t stream, bool tally, const WfTuning& tn, WfImagePlan* ran) {
   // QUADS: solids outside the hierarchies, or the hierarchy over the other records
   const bool quads = sc.n_fx_quads > 0 || sc.n_obvh > 0 || sc.n_lbvh > 0;
+  if (sc.n_tris > 0)  // (their kernels are the QUADS ones with the triangle loop and walk)
+    return tally ? launch_fused_q<true, true, true>(sc, cam, a, primary, n, stream, tn, ran)
+                 : launch_fused_q<true, false, true>(sc, cam, a, primary, n, stream, tn, ran);
   if (tally)
     return quads ? launch_fused_q<true, true>(sc, cam, a, primary, n, stream, tn, ran)
                  : launch_fused_q<false, true>(sc, cam, a, primary, n, stream, tn, ran);
@@ -410,7 +413,7 @@ hipError_t Wavefront::render(const DevScene& sc, const WfJob& job, hipStream_t s
   // reference's every-shape loop is asked for; counting never changes the algorithm
   const bool exhaustive = (flags & WF_EXHAUSTIVE) != 0;
   const bool count = (flags & WF_COUNT) != 0;
-  const bool bvh = tn.accel != 0 && !exhaustive && (sc.n_bvh > 0 || sc.n_obvh > 0 || sc.n_lbvh > 0);
+  const bool bvh = tn.accel != 0 && !exhaustive && (sc.n_bvh > 0 || sc.n_obvh > 0 || sc.n_lbvh > 0 || sc.n_tbvh > 0);
   const bool fused = bvh;
   // (a counted render of a scene with groups traces every shadow ray: the reference's shape
   // tests then come from the group gates each ray met, GateSkips)
@@ -452,7 +455,7 @@ hipError_t Wavefront::render(const DevScene& sc, const WfJob& job, hipStream_t s
   lr_.L = (unsigned)sc.n_lights; lr_.n0 = n0; lr_.max_depth = max_depth;
   lr_.counted = count; lr_.exact_disc = !bvh && !skip_shadow; lr_.bvh = bvh;
   lr_.n_diag = (unsigned long long)sc.n_diag; lr_.n_gen = (unsigned long long)sc.n_gen;
-  lr_.n_planes = (unsigned long long)sc.n_planes; lr_.n_quads = (unsigned long long)sc.n_quads;
+  lr_.n_planes = (unsigned long long)sc.n_planes; lr_.n_quads = (unsigned long long)sc.n_quads + (unsigned long long)sc.n_tris;
   return hipSuccess;
 }
 
@@ -672,7 +675,7 @@ hipError_t Wavefront::render_exhaustive(const DevScene& sc, const WfJob& job, hi
     a.disc_slot = (unsigned)ccls;
     prof_rays_[ccls] += n;
     WF_CHECK(pmark(stream, ccls, true));
-    if (sc.n_quads > 0) WF_CHECK(launch_closest_exh<true>(sc, cam, a, prim_launch, gen_lds, n, stream, tn));
+    if (sc.n_quads > 0 || sc.n_tris > 0) WF_CHECK(launch_closest_exh<true>(sc, cam, a, prim_launch, gen_lds, n, stream, tn));
     else WF_CHECK(launch_closest_exh<false>(sc, cam, a, prim_launch, gen_lds, n, stream, tn));
     WF_CHECK(pmark(stream, ccls, false));
     // 2. prepare_computations + spawn
@@ -705,7 +708,7 @@ hipError_t Wavefront::render_exhaustive(const DevScene& sc, const WfJob& job, hi
         forked = true;
       }
       WF_CHECK(pmark(sh_stream, WF_SHADOW, true));
-      if (sc.n_quads > 0) WF_CHECK(launch_shadow_exh<true>(sc, a, gen_lds, sh_stream, tn));
+      if (sc.n_quads > 0 || sc.n_tris > 0) WF_CHECK(launch_shadow_exh<true>(sc, a, gen_lds, sh_stream, tn));
       else WF_CHECK(launch_shadow_exh<false>(sc, a, gen_lds, sh_stream, tn));
       WF_CHECK(pmark(sh_stream, WF_SHADOW, false));
     }

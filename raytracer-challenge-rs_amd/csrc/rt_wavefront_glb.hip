@@ -10,10 +10,15 @@
 namespace rtamd {
 
 template <int LANE>
-static hipError_t launch_glb_lane(bool quads, bool tally, bool cam_rays, const DevScene& sc, const DevCamera& cam,
+static hipError_t launch_glb_lane(bool quads, bool tris, bool tally, bool cam_rays, const DevScene& sc, const DevCamera& cam,
                                   const WfArgs& a, size_t dyn, unsigned n, hipStream_t stream, int block, hipEvent_t e0,
                                   hipEvent_t e1) {
 #define RT_GLB(Q, T, C) wf_launch(wf_trace_fused<false, Q, LANE, T, C>, block, dyn, n, stream, e0, e1, sc, cam, a)
+#define RT_GLB_TRI(T, C) wf_launch(wf_trace_fused<false, true, LANE, T, C, true>, block, dyn, n, stream, e0, e1, sc, cam, a)
+  if (tris) {  // a scene with triangles: the QUADS kernels with the triangle loop and walk
+    if (cam_rays) return tally ? RT_GLB_TRI(true, true) : RT_GLB_TRI(false, true);
+    return tally ? RT_GLB_TRI(true, false) : RT_GLB_TRI(false, false);
+  }
   if (cam_rays) {
     if (quads) return tally ? RT_GLB(true, true, true) : RT_GLB(true, false, true);
     return tally ? RT_GLB(false, true, true) : RT_GLB(false, false, true);
@@ -21,11 +26,12 @@ static hipError_t launch_glb_lane(bool quads, bool tally, bool cam_rays, const D
   if (quads) return tally ? RT_GLB(true, true, false) : RT_GLB(true, false, false);
   return tally ? RT_GLB(false, true, false) : RT_GLB(false, false, false);
 #undef RT_GLB
+#undef RT_GLB_TRI
 }
-hipError_t wf_launch_global(int lane, bool quads, bool tally, bool cam_rays, const DevScene& sc, const DevCamera& cam,
+hipError_t wf_launch_global(int lane, bool quads, bool tris, bool tally, bool cam_rays, const DevScene& sc, const DevCamera& cam,
                             const WfArgs& a, size_t dyn, unsigned n, hipStream_t stream, int block, hipEvent_t e0,
                             hipEvent_t e1) {
-#define RT_LANE(L) launch_glb_lane<L>(quads, tally, cam_rays, sc, cam, a, dyn, n, stream, block, e0, e1)
+#define RT_LANE(L) launch_glb_lane<L>(quads, tris, tally, cam_rays, sc, cam, a, dyn, n, stream, block, e0, e1)
   if (lane == kLaneLdsStack) return RT_LANE(kLaneLdsStack);
   if (lane == kLaneScratch) return RT_LANE(kLaneScratch);
   if (lane == kLaneWide16) return RT_LANE(kLaneWide16);

@@ -377,6 +377,11 @@ __device__ __forceinline__ void wf_trace_lds(const DevScene& sc, const WfLds& lv
       if (qr[j].gate && !group_gate(sc, qr[j].gate, o, d)) { ++sk.other; continue; }
       quad_test<SHADOW>(qr + j, o, d, h);
     }
+    cTriRec tr = (cTriRec)sc.tris;  // triangles: scalar loads
+    for (int j = 0; j < sc.n_tris; ++j) {
+      if (tr[j].gate && !group_gate(sc, tr[j].gate, o, d)) { ++sk.other; continue; }
+      tri_test<SHADOW>(tr + j, o, d, h);
+    }
   }
   hit_finish(h);
 }
@@ -410,7 +415,7 @@ __global__ __launch_bounds__(kTraceBlock, TW) void wf_trace_closest(DevScene sc,
     wf_ray(a, cam, slot, o, d);
     Hit h;
     if constexpr (USE_LDS) wf_trace_lds<PRIMARY, false, QUADS>(sc, lv, o, d, h, n_disc, sk);
-    else trace<false>(sc, o, d, h, n_disc, &sk);
+    else trace<false, QUADS>(sc, o, d, h, n_disc, &sk);
     WfHit w;
     w.t = h.t; w.key = h.key; w.c1k = h.c1k; w.c2k = h.c2k; w.hin = h.hin;
     a.hits[slot] = w;
@@ -441,7 +446,7 @@ __global__ __launch_bounds__(kTraceBlock, TW) void wf_trace_shadow(DevScene sc, 
     shadow_ray(sc, a, shard_slot<false>(pre, a.sh_cap, i), o, d, dist, slot);
     Hit h;
     if constexpr (USE_LDS) wf_trace_lds<false, true, QUADS>(sc, lv, o, d, h, n_disc, sk);
-    else trace<true>(sc, o, d, h, n_disc, &sk);
+    else trace<true, QUADS>(sc, o, d, h, n_disc, &sk);
     shadow_result(sc, a, slot, h.key >= 0 && h.t < dist, o, d);
   }
   const unsigned long long s = wave_sum(n_disc);
@@ -660,7 +665,8 @@ struct FusedTally {
 // either the final colour (no children) or a ParentRec. Every lane of the wave
 // calls it (shard_append), `valid` false for the padding lanes. TALLY: the
 // kernel's (a counted launch; shadow_trace then counts every group gate).
-template <bool QUADS, bool CAM, bool TALLY, typename Image>
+// TRIS: the kernel's (a scene with triangles).
+template <bool QUADS, bool CAM, bool TALLY, bool TRIS, typename Image>
 __device__ __forceinline__ void shade_fused(const DevScene& sc, const DevCamera& cam, const WfArgs& a,
                                             const Image& img, unsigned q, unsigned slot, bool valid, V3 o, V3 d,
                                             const Hit& h, FusedTally& t) {
@@ -671,7 +677,7 @@ __device__ __forceinline__ void shade_fused(const DevScene& sc, const DevCamera&
   V3 refr_dir = v3(0, 0, 0);
   const ShadeRec* m = nullptr;
   if (valid && h.key >= 0) {
-    c = prepare(sc, o, d, h);
+    c = prepare<TRIS>(sc, o, d, h);
     hit = true;
     m = &sc.shade[c.obj];
     // reflected_color (world.rs:107-114)
@@ -729,10 +735,10 @@ __device__ __forceinline__ void shade_fused(const DevScene& sc, const DevCamera&
     if (a.skip_shadow && shadow_irrelevant(*m, Lr, sdir, c.normal, term)) {
       // the light is behind the surface: lighting() is the ambient term either way
     } else {
-      const bool shadowed = shadow_trace<QUADS, TALLY>(
+      const bool shadowed = shadow_trace<QUADS, TALLY, TRIS>(
           sc, a.use_lb, img, l, c.over, sdir, dist, t.sh_disc, t.sh_tests, t.sh_boxes, &t.gsk, own_first,
           own_out >= 0 && vdot(sdir, c.normal) >= 0.0 ? own_out : -1);
-      if (QUADS && a.count) count_hier_gates(sc, c.over, sdir, t.gsk);
+      if (QUADS && a.count) count_hier_gates<TRIS>(sc, c.over, sdir, t.gsk);
       ++t.sh_rays;
       term = lighting(*m, Lr, c.over, c.eyev, c.normal, shadowed, sdir);
     }
@@ -760,7 +766,10 @@ __device__ __forceinline__ void shade_fused(const DevScene& sc, const DevCamera&
 // per-visit and per-test counting and the wave-end atomics altogether: C3
 // 1.021 -> 0.964 ms/frame, an 8-way shard 0.204 -> 0.184 ms.
 // CAM: the launch may read camera rays (generation 0 of a camera render).
-template <bool PRIMARY, bool QUADS, int LANE, bool TALLY, bool CAM = PRIMARY>
+// TRIS (with QUADS): the scene has triangles. A flag of its own, so that the kernels of
+// scenes with solids and no triangle keep the registers and scratch they had without the
+// triangle walk (profiles/mesh_resources.txt).
+template <bool PRIMARY, bool QUADS, int LANE, bool TALLY, bool CAM = PRIMARY, bool TRIS = false>
 __global__ __launch_bounds__(kTraceBlock, 4) void wf_trace_fused(DevScene sc, DevCamera cam, WfArgs a) {
   __shared__ int stack_lds[lane_static_lds_bytes(LANE) ? lane_static_lds_bytes(LANE) / 4 : 1];  // (1: never read)
   extern __shared__ __attribute__((aligned(16))) unsigned char lane_dyn[];
@@ -819,7 +828,7 @@ __global__ __launch_bounds__(kTraceBlock, 4) void wf_trace_fused(DevScene sc, De
     hit_init(h);
     if (valid) {
       wf_ray<CAM>(a, cam, slot, o, d);
-      if constexpr (TALLY && QUADS) count_hier_gates(sc, o, d, t.gsk);
+      if constexpr (TALLY && QUADS) count_hier_gates<TRIS>(sc, o, d, t.gsk);
       if constexpr (!Image::kPerLane) {
         // the chunk's frame (chunks never mix frames): its shared-origin primary records
         const unsigned pf = a.n_frames > 1 ? (c * 64u) / a.frame_rays : 0u;
@@ -827,11 +836,12 @@ __global__ __launch_bounds__(kTraceBlock, 4) void wf_trace_fused(DevScene sc, De
                                       t.tests, t.boxes);
       }
       // (a per-lane walk: planes and the other records first, an early nearest hit tightens the culling)
-      trace_rest<false, QUADS, true>(sc, o, d, h, t.disc, &t.gsk);
+      trace_rest<false, QUADS, true, TRIS>(sc, o, d, h, t.disc, &t.gsk);
       if constexpr (QUADS) {
         other_trace<false>(sc, o, d, 0.0, h, t.disc, t.tests, t.boxes);
         line_trace<false>(sc, o, d, 0.0, h, t.tests, t.boxes);
       }
+      if constexpr (TRIS) tri_trace<false>(sc, o, d, 0.0, h, t.tests, t.boxes);
       if constexpr (Image::kPerLane) img.template walk<false>(sc, o, d, 0.0, h, t.disc, t.tests, t.boxes);
     }
     hit_finish(h);
@@ -846,7 +856,7 @@ __global__ __launch_bounds__(kTraceBlock, 4) void wf_trace_fused(DevScene sc, De
     V3 o = v3(0, 0, 0), d = v3(0, 0, 0);
     Hit h;
     traverse(i, valid, slot, o, d, h);
-    shade_fused<QUADS, CAM, TALLY>(sc, cam, a, img, c, slot, valid, o, d, h, t);
+    shade_fused<QUADS, CAM, TALLY, TRIS>(sc, cam, a, img, c, slot, valid, o, d, h, t);
     c = dyn ? c_base + X * (unsigned)__shfl((int)k_next, 0, 64) : c + W;
   }
   if constexpr (!TALLY) return;

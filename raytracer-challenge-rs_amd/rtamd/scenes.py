@@ -680,3 +680,73 @@ def fuzz(seed, width=64, height=48, n_spheres=None):
     frm = (u(-6, 6), u(0.5, 5), u(-10, -4))
     to = (u(-1, 1), u(0.3, 1.5), u(0, 3))
     return w, _camera(width, height, u(0.6, 1.6), frm, to), rnd.randrange(1, 7)
+
+
+def mesh_torus(nu=10, nv=10, smooth=False, seed=0x5EED0007, major=1.0, minor=0.4):
+    """OBJ text of a torus about the y axis: nu x nv quads, each split into two
+    faces (2 nu nv triangles). `smooth`: `vn` records and `f a//a` faces
+    (SmoothTriangle), else plain faces (Triangle). The vertices are moved off
+    the exact torus by up to 1e-3 (splitmix64 from `seed`), so no two of them
+    share a coordinate. Numbers are written with repr(), which the parser reads
+    back bit for bit."""
+    rng = SplitMix64(seed)
+    lines = ["# torus %d x %d" % (nu, nv)]
+    for i in range(nu):
+        a = 2.0 * PI * i / nu
+        for j in range(nv):
+            b = 2.0 * PI * j / nv
+            r = major + minor * math.cos(b)
+            p = (r * math.cos(a) + 1e-3 * rng.u(), minor * math.sin(b) + 1e-3 * rng.u(), r * math.sin(a) + 1e-3 * rng.u())
+            lines.append("v %r %r %r" % p)
+    if smooth:
+        for i in range(nu):
+            a = 2.0 * PI * i / nu
+            for j in range(nv):
+                b = 2.0 * PI * j / nv
+                lines.append("vn %r %r %r" % (math.cos(b) * math.cos(a), math.sin(b), math.cos(b) * math.sin(a)))
+    vid = lambda i, j: 1 + (i % nu) * nv + (j % nv)
+    ref = (lambda k: "%d//%d" % (k, k)) if smooth else (lambda k: "%d" % k)
+    for i in range(nu):
+        for j in range(nv):
+            q = [vid(i, j), vid(i + 1, j), vid(i + 1, j + 1), vid(i, j + 1)]
+            lines.append("f %s %s %s" % (ref(q[0]), ref(q[1]), ref(q[2])))
+            lines.append("f %s %s %s" % (ref(q[0]), ref(q[2]), ref(q[3])))
+    return "\n".join(lines) + "\n"
+
+
+def mesh_scene(width=640, height=360, nu=64, nv=64, smooth=True, divide=5, seed=0x5EED0007, depth=5):
+    """A mesh scene: mesh_torus(nu, nv, smooth) parsed by the OBJ parser into one
+    group (slightly transparent, reflective), divided with threshold `divide`
+    (0: not divided), then rotated and scaled (every level of the divided group
+    bakes the transform into its descendants, group.rs:71-94: about 20 s of host
+    time for 8 000 triangles); a reflective floor plane, a glass
+    sphere beside the torus, one loose triangle that casts no shadow, two
+    lights. Returns (obj_text, world, camera, depth)."""
+    text = mesh_torus(nu, nv, smooth, seed)
+    g = rt.parse_obj_string(text).as_group()
+    m = rt.Material()
+    m.color = rt.Color(0.9, 0.45, 0.2)
+    m.reflective = 0.15
+    m.transparency = 0.3
+    m.refractive_index = 1.3
+    g.set_material(m)
+    if divide:
+        g.divide(divide)
+    g.set_transform(rt.translation(0.0, 1.1, 0.0) * rt.rotation_x(0.6) * rt.rotation_z(0.3) * rt.scaling(1.2, 1.2, 1.0))
+    w = rt.World()
+    floor = rt.Plane()
+    floor.material.color = rt.Color(0.8, 0.8, 0.85)
+    floor.material.reflective = 0.4
+    floor.material.specular = 0.0
+    w.add_object(floor)
+    w.add_object(g)
+    ball = rt.glass_sphere()
+    ball.set_transform(rt.translation(2.1, 0.7, -0.6) * rt.scaling(0.7, 0.7, 0.7))
+    w.add_object(ball)
+    fin = rt.Triangle(rt.Point(-2.6, 0.0, 0.5), rt.Point(-1.6, 0.0, -0.4), rt.Point(-2.0, 1.8, 0.2))
+    fin.material.color = rt.Color(0.2, 0.6, 0.9)
+    fin.no_shadow()
+    w.add_object(fin)
+    w.add_light(rt.PointLight(rt.Point(-6.0, 8.0, -8.0), rt.Color(0.8, 0.8, 0.8)))
+    w.add_light(rt.PointLight(rt.Point(5.0, 6.0, -3.0), rt.Color(0.4, 0.4, 0.5)))
+    return text, w, _camera(width, height, PI / 3.0, (0.0, 2.6, -6.0), (0.0, 0.9, 0.0)), depth
