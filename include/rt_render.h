@@ -126,6 +126,39 @@ typedef struct rt_group_desc {
   int32_t _pad;
 } rt_group_desc;
 
+/* (ABI 6, additive) A container of the flattened World for rt_scene_create_tree: a
+ * `Group` (geometry/shape/group.rs:13-18) or a `Csg` (geometry/shape/csg.rs:43-49).
+ * Nodes are listed parents first.
+ *   parent     the node that holds it (-1: a member of World::objects)
+ *   side       when the parent is a Csg: 0 = its `left`, 1 = its `right`
+ *   operation  RT_CSG_* of a Csg (csg.rs:14-19)
+ *   min, max   get_bounds() as the node's intersect tests it: a Group's as
+ *              rt_group_desc; a Csg's as Csg::local_intersect tests it against the
+ *              LOCAL ray (csg.rs:115-118): Csg::new's union of the children's
+ *              parent_space_bounds() (csg.rs:57-59), re-derived by the default
+ *              set_transform (geometry/mod.rs:74-85). Box and ray of a
+ *              transformed Csg are therefore in different spaces, as there.
+ *   inverse    a Csg's own transform_inverse: Shape::intersect transforms the ray
+ *              by it (geometry/mod.rs:46-49) before the children transform it
+ *              again by theirs. Ignored for a Group (its transform is baked
+ *              into its children, group.rs:71-94,128-133; into a Csg child's OWN
+ *              transform, not into that Csg's leaves). */
+enum { RT_NODE_GROUP = 0, RT_NODE_CSG = 1 };
+enum { RT_CSG_UNION = 0, RT_CSG_INTERSECTION = 1, RT_CSG_DIFFERENCE = 2 };
+typedef struct rt_node_desc {
+  int32_t kind, parent;
+  int32_t side, operation;
+  double min[3], max[3];
+  double inverse[16];
+} rt_node_desc;
+
+/* Compile-time caps of the Csg evaluation (one per-ray survivor list of
+ * RT_CSG_MAX_LEAVES * 4 entries): the primitives under one Csg that has no Csg
+ * above it, and the Csg nodes on any path down from it (Groups between them
+ * are free). rt_scene_create_tree refuses a world beyond either. */
+#define RT_CSG_MAX_LEAVES 16
+#define RT_CSG_MAX_DEPTH 4
+
 /* The vertices of a `Triangle` (triangle.rs:24-44) or `SmoothTriangle`
  * (smooth_triangle.rs:27-55) in object space; its rt_shape_desc carries the
  * transform and the material. The library derives e1 = p2 - p1, e2 = p3 - p1
@@ -234,6 +267,28 @@ int rt_scene_create_groups(const rt_shape_desc* shapes, size_t n_shapes,
 int rt_scene_create_mesh(const rt_shape_desc* shapes, size_t n_shapes,
                          const int32_t* shape_group, const rt_group_desc* groups,
                          size_t n_groups, const rt_triangle_desc* tris, size_t n_tris,
+                         const rt_light_desc* lights, size_t n_lights, int device,
+                         rt_scene** out);
+/* (ABI 6, additive) rt_scene_create_mesh for a World that also holds `Csg`s
+ * (csg.rs), anywhere in World::objects or inside Groups: `shapes` are the
+ * primitives in the order the reference reaches them (depth first, a Group's
+ * children in order, a Csg's left before its right); shape_node[i] is the
+ * innermost node of shape i (-1: none) and shape_side[i] its side when that
+ * node is a Csg (shape_side may be NULL when no shape's node is one). The
+ * other three rt_scene_create* are this call without Csg nodes.
+ * A Csg's intersections are the reference's: the ray transformed down the
+ * chain one matrix after another, every box gate, left ++ right sorted (ties:
+ * left's before right's, each list in its own order) and filtered by
+ * Csg::filter_intersections (csg.rs:71-91), nested Csgs bottom-up; normals,
+ * patterns, materials and has_shadow are the leaf's own (geometry/mod.rs:51-56;
+ * the enclosing Csgs' transforms take no part, as there).
+ * RT_ERR_UNSUPPORTED_SHAPE: a Triangle / SmoothTriangle under a Csg; more than
+ * RT_CSG_MAX_LEAVES primitives under one outermost Csg; more than
+ * RT_CSG_MAX_DEPTH nested Csgs. The message names the cap. */
+int rt_scene_create_tree(const rt_shape_desc* shapes, size_t n_shapes,
+                         const int32_t* shape_node, const int32_t* shape_side,
+                         const rt_node_desc* nodes, size_t n_nodes,
+                         const rt_triangle_desc* tris, size_t n_tris,
                          const rt_light_desc* lights, size_t n_lights, int device,
                          rt_scene** out);
 void rt_scene_destroy(rt_scene* scene);
@@ -433,6 +488,7 @@ int rt_device_count(void);
 size_t rt_sizeof_shape_desc(void);  /* 680 */
 size_t rt_sizeof_camera_desc(void); /* 160 */
 size_t rt_sizeof_stats(void);       /* 112 */
+size_t rt_sizeof_node_desc(void);   /* 192 */
 
 /* Waits for every render issued on `scene` (on any stream) and reports any
  * frame the library found incomplete after the fact. The wavefront queues of

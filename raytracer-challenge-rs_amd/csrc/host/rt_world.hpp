@@ -243,10 +243,13 @@ inline rt_triangle_desc to_triangle_desc(const Shape& s) {
 // children's set_transform with the product, group.rs:71-94,128-133), so a
 // child's transform is final; its box is the union of its children's boxes.
 struct Group;
-struct GroupChild {  // Box<dyn Shape> of a Group: a primitive or a group
+struct Csg;
+struct GroupChild {  // Box<dyn Shape> of a Group, a Csg or the World: a primitive, a group or a csg
   std::shared_ptr<Shape> shape;
   std::shared_ptr<Group> group;
+  std::shared_ptr<Csg> csg;
 };
+GroupChild clone_child(const GroupChild& c);  // a deep copy (Box<dyn Shape> owns its shape)
 struct Group {
   Matrix transform = Matrix::identity(4, 4);
   Matrix transform_inverse = Matrix::identity(4, 4);
@@ -260,9 +263,7 @@ struct Group {
   Group(const Group& o)
       : transform(o.transform), transform_inverse(o.transform_inverse), material(o.material), bbox(o.bbox) {
     children.reserve(o.children.size());
-    for (const GroupChild& c : o.children)
-      children.push_back(c.shape ? GroupChild{std::make_shared<Shape>(*c.shape), nullptr}
-                                 : GroupChild{nullptr, std::make_shared<Group>(*c.group)});
+    for (const GroupChild& c : o.children) children.push_back(clone_child(c));
   }
   Group& operator=(const Group& o) {
     if (this != &o) {
@@ -275,8 +276,9 @@ struct Group {
   Group& operator=(Group&&) = default;
   void set_transform(const Matrix& t);                          // group.rs:71-94
   void set_material(const Material& m);                         // group.rs:96-102
-  void add_child(const Shape& s) { add(GroupChild{std::make_shared<Shape>(s), nullptr}); }  // group.rs:128-133
-  void add_child(const Group& g) { add(GroupChild{nullptr, std::make_shared<Group>(g)}); }
+  void add_child(const Shape& s) { add(GroupChild{std::make_shared<Shape>(s), nullptr, nullptr}); }  // group.rs:128-133
+  void add_child(const Group& g) { add(GroupChild{nullptr, std::make_shared<Group>(g), nullptr}); }
+  void add_child(const Csg& c);  // the Csg's own transform takes the product; nothing is baked into its leaves
   BoundingBox parent_space_bounds() const { return bbox.transform(Matrix::identity(4, 4)); }
   // group.rs:108-122: children whose parent-space box fits one half of this box
   // move into a new subgroup per half (partition_children :135-189,
@@ -287,12 +289,81 @@ struct Group {
  private:
   void add(GroupChild c);
 };
-inline const Matrix& child_transform(const GroupChild& c) { return c.shape ? c.shape->transform : c.group->transform; }
-inline const BoundingBox& child_bounds(const GroupChild& c) { return c.shape ? c.shape->bbox : c.group->bbox; }
+// geometry/shape/csg.rs:14-140. `left` / `right`: a shape, a group or a csg. The
+// transform, material and shadow flag are the Csg's own BaseShape: set_transform is
+// the trait's default (geometry/mod.rs:74-85: only the Csg's own matrices and box
+// change), set_material reaches only its own, unused material (:66-68).
+enum class Operation { Union = RT_CSG_UNION, Intersection = RT_CSG_INTERSECTION, Difference = RT_CSG_DIFFERENCE };
+struct Csg {
+  Operation operation = Operation::Union;
+  Matrix transform = Matrix::identity(4, 4);
+  Matrix transform_inverse = Matrix::identity(4, 4);
+  Material material;
+  BoundingBox bbox;
+  GroupChild left, right;
+  template <typename L, typename R>
+  Csg(Operation op, const L& l, const R& r);  // csg.rs:52-69
+  Csg(const Csg& o)
+      : operation(o.operation), transform(o.transform), transform_inverse(o.transform_inverse), material(o.material),
+        bbox(o.bbox), left(clone_child(o.left)), right(clone_child(o.right)) {}
+  Csg& operator=(const Csg& o) {
+    if (this != &o) {
+      Csg t(o);
+      *this = std::move(t);
+    }
+    return *this;
+  }
+  Csg(Csg&&) = default;
+  Csg& operator=(Csg&&) = default;
+  void set_transform(const Matrix& t) {  // geometry/mod.rs:74-85
+    bbox = bbox.transform(transform_inverse);
+    const Matrix inv = t.inverse();
+    transform_inverse = inv;
+    transform = t;
+    bbox = bbox.transform(transform);
+  }
+  void set_material(const Material& m) { material = m; }  // geometry/mod.rs:66-68
+  BoundingBox parent_space_bounds() const { return bbox.transform(Matrix::identity(4, 4)); }
+  void divide(size_t threshold);           // csg.rs:136-139
+  // csg.rs:132-134, pointer identity down the tree. For completeness of the mirror only: nothing on the
+  // render path calls it (the device's filter decides `left.includes` by object index, rt_csg.hpp), and
+  // the Python module, whose children are copies, does not bind it.
+  bool includes(const Shape* s) const;
+};
+inline GroupChild make_child(const Shape& s) { return GroupChild{std::make_shared<Shape>(s), nullptr, nullptr}; }
+inline GroupChild make_child(const Group& g) { return GroupChild{nullptr, std::make_shared<Group>(g), nullptr}; }
+inline GroupChild make_child(const Csg& c) { return GroupChild{nullptr, nullptr, std::make_shared<Csg>(c)}; }
+inline GroupChild clone_child(const GroupChild& c) {
+  return c.shape ? make_child(*c.shape) : c.group ? make_child(*c.group) : c.csg ? make_child(*c.csg) : GroupChild{};
+}
+inline const Matrix& child_transform(const GroupChild& c) {
+  return c.shape ? c.shape->transform : c.group ? c.group->transform : c.csg->transform;
+}
+inline const BoundingBox& child_bounds(const GroupChild& c) {
+  return c.shape ? c.shape->bbox : c.group ? c.group->bbox : c.csg->bbox;
+}
+inline BoundingBox child_parent_space_bounds(const GroupChild& c) {
+  return child_bounds(c).transform(Matrix::identity(4, 4));
+}
 inline void child_set_transform(GroupChild& c, const Matrix& t) {
   if (c.shape) c.shape->set_transform(t);
-  else c.group->set_transform(t);
+  else if (c.group) c.group->set_transform(t);
+  else c.csg->set_transform(t);
 }
+inline void child_divide(GroupChild& c, size_t threshold);
+// Shape::includes (geometry/mod.rs:87-89), Group's (group.rs:104-106), Csg's (csg.rs:132-134)
+inline bool child_includes(const GroupChild& c, const Shape* s);
+template <typename L, typename R>
+Csg::Csg(Operation op, const L& l, const R& r) : operation(op), left(make_child(l)), right(make_child(r)) {
+  bbox.add_box(child_parent_space_bounds(left));
+  bbox.add_box(child_parent_space_bounds(right));
+}
+inline void Csg::divide(size_t threshold) {
+  child_divide(left, threshold);
+  child_divide(right, threshold);
+}
+inline bool Csg::includes(const Shape* s) const { return child_includes(left, s) || child_includes(right, s); }
+inline void Group::add_child(const Csg& c) { add(make_child(c)); }
 inline void Group::set_transform(const Matrix& t) {
   const Matrix inverse_old = transform_inverse;  // remove the current transform from the children
   for (GroupChild& c : children) child_set_transform(c, inverse_old * child_transform(c));
@@ -310,12 +381,13 @@ inline void Group::set_material(const Material& m) {
   material = m;
   for (GroupChild& c : children) {
     if (c.shape) c.shape->set_material(m);
-    else c.group->set_material(m);
+    else if (c.group) c.group->set_material(m);
+    else c.csg->set_material(m);
   }
 }
 inline void Group::add(GroupChild c) {
   child_set_transform(c, transform * child_transform(c));
-  const BoundingBox cbox = c.shape ? c.shape->parent_space_bounds() : c.group->parent_space_bounds();
+  const BoundingBox cbox = child_parent_space_bounds(c);
   bbox.add_box(cbox);
   children.push_back(std::move(c));
 }
@@ -327,7 +399,7 @@ inline void Group::divide(size_t threshold) {
       const BoundingBox& hb = h ? halves.second : halves.first;
       std::vector<GroupChild> keep;
       for (GroupChild& c : children) {
-        const BoundingBox cb = c.shape ? c.shape->parent_space_bounds() : c.group->parent_space_bounds();
+        const BoundingBox cb = child_parent_space_bounds(c);
         (hb.contains_box(cb) ? part[h] : keep).push_back(std::move(c));
       }
       children = std::move(keep);
@@ -336,11 +408,21 @@ inline void Group::divide(size_t threshold) {
       if (part[h].empty()) continue;
       auto g = std::make_shared<Group>();
       for (GroupChild& c : part[h]) g->add(std::move(c));
-      children.push_back(GroupChild{nullptr, std::move(g)});
+      children.push_back(GroupChild{nullptr, std::move(g), nullptr});
     }
   }
-  for (GroupChild& c : children)
-    if (c.group) c.group->divide(threshold);
+  for (GroupChild& c : children) child_divide(c, threshold);
+}
+inline void child_divide(GroupChild& c, size_t threshold) {
+  if (c.group) c.group->divide(threshold);
+  else if (c.csg) c.csg->divide(threshold);
+}
+inline bool child_includes(const GroupChild& c, const Shape* s) {
+  if (c.shape) return c.shape.get() == s;
+  if (c.csg) return c.csg->includes(s);
+  for (const GroupChild& k : c.group->children)
+    if (child_includes(k, s)) return true;
+  return false;
 }
 
 // canvas.rs:8-52 + image/ppm.rs
@@ -464,18 +546,20 @@ class World {
     w->add_object(s2);
     return w;
   }
-  void add_object(const Shape& s) { drop(); objects_.push_back(GroupChild{std::make_shared<Shape>(s), nullptr}); }  // :87-89
-  void add_object(const Group& g) { drop(); objects_.push_back(GroupChild{nullptr, std::make_shared<Group>(g)}); }
+  void add_object(const Shape& s) { drop(); objects_.push_back(make_child(s)); }  // :87-89
+  void add_object(const Group& g) { drop(); objects_.push_back(make_child(g)); }
+  void add_object(const Csg& c) { drop(); objects_.push_back(make_child(c)); }
   void add_light(const PointLight& l) { drop(); lights_.push_back(l); }  // :83-85
   size_t n_objects() const { return objects_.size(); }
   size_t n_lights() const { return lights_.size(); }
   Shape& object(size_t i) {
     drop();
-    if (!objects_.at(i).shape) throw std::invalid_argument("World::object: object is a Group");
+    if (!objects_.at(i).shape) throw std::invalid_argument(not_a_primitive(objects_[i]));
     return *objects_[i].shape;
   }
+  const GroupChild& child_c(size_t i) const { return objects_.at(i); }
   const Shape& object_c(size_t i) const {
-    if (!objects_.at(i).shape) throw std::invalid_argument("World::object: object is a Group");
+    if (!objects_.at(i).shape) throw std::invalid_argument(not_a_primitive(objects_[i]));
     return *objects_[i].shape;
   }
   PointLight& light(size_t i) { drop(); return lights_.at(i); }
@@ -484,35 +568,64 @@ class World {
   // children in order), the innermost group of each (-1: none), and the groups
   // (their boxes, parents first); the vertices of the triangles among the
   // primitives, in their order.
+  // With a Csg anywhere (rt_scene_create_tree): `nodes` holds the groups and the
+  // csgs, parents first, `shape_group` each primitive's innermost node and
+  // `shape_side` its side under a Csg (a Csg's left is walked before its right);
+  // `groups` is then left empty.
   struct Flat {
     std::vector<rt_shape_desc> shapes;
     std::vector<int32_t> shape_group;
     std::vector<rt_group_desc> groups;
     std::vector<rt_triangle_desc> tris;
+    std::vector<rt_node_desc> nodes;
+    std::vector<int32_t> shape_side;
+    bool has_csg = false;
   };
   Flat flatten() const {
     Flat f;
     struct Walk {
       Flat& f;
-      void node(const GroupChild& c, int32_t parent) {
+      void node(const GroupChild& c, int32_t parent, int32_t side) {
         if (c.shape) {
           f.shapes.push_back(to_desc(*c.shape));
           f.shape_group.push_back(parent);
+          f.shape_side.push_back(side);
           if (c.shape->kind >= RT_SHAPE_TRIANGLE) f.tris.push_back(to_triangle_desc(*c.shape));
           return;
         }
-        rt_group_desc g;
-        std::memset(&g, 0, sizeof g);
-        const BoundingBox& b = c.group->bbox;
-        g.min[0] = b.min.x; g.min[1] = b.min.y; g.min[2] = b.min.z;
-        g.max[0] = b.max.x; g.max[1] = b.max.y; g.max[2] = b.max.z;
-        g.parent = parent;
-        f.groups.push_back(g);
-        const int32_t me = (int32_t)f.groups.size() - 1;
-        for (const GroupChild& k : c.group->children) node(k, me);
+        rt_node_desc n;
+        std::memset(&n, 0, sizeof n);
+        const BoundingBox& b = c.group ? c.group->bbox : c.csg->bbox;
+        n.min[0] = b.min.x; n.min[1] = b.min.y; n.min[2] = b.min.z;
+        n.max[0] = b.max.x; n.max[1] = b.max.y; n.max[2] = b.max.z;
+        n.parent = parent;
+        n.side = side;
+        n.kind = c.group ? RT_NODE_GROUP : RT_NODE_CSG;
+        if (c.csg) {
+          n.operation = (int32_t)c.csg->operation;
+          std::memcpy(n.inverse, c.csg->transform_inverse.data(), sizeof n.inverse);
+          f.has_csg = true;
+        }
+        f.nodes.push_back(n);
+        const int32_t me = (int32_t)f.nodes.size() - 1;
+        if (c.group) {
+          for (const GroupChild& k : c.group->children) node(k, me, 0);
+        } else {  // Csg::local_intersect: left, then right (csg.rs:120-121)
+          node(c.csg->left, me, 0);
+          node(c.csg->right, me, 1);
+        }
       }
     } w{f};
-    for (const GroupChild& c : objects_) w.node(c, -1);
+    for (const GroupChild& c : objects_) w.node(c, -1, 0);
+    if (!f.has_csg) {  // groups only: rt_scene_create_mesh's arrays
+      f.groups.resize(f.nodes.size());
+      for (size_t g = 0; g < f.nodes.size(); ++g) {
+        std::memset(&f.groups[g], 0, sizeof f.groups[g]);
+        std::memcpy(f.groups[g].min, f.nodes[g].min, sizeof f.groups[g].min);
+        std::memcpy(f.groups[g].max, f.nodes[g].max, sizeof f.groups[g].max);
+        f.groups[g].parent = f.nodes[g].parent;
+      }
+    }
     return f;
   }
   std::vector<rt_shape_desc> descs() const { return flatten().shapes; }
@@ -538,9 +651,15 @@ class World {
       const Flat f = flatten();
       auto l = light_descs();
       rt_scene* s = nullptr;
-      check(rt_scene_create_mesh(f.shapes.data(), f.shapes.size(), f.shape_group.data(), f.groups.data(),
-                                 f.groups.size(), f.tris.data(), f.tris.size(), l.data(), l.size(), device, &s),
-            "rt_scene_create");
+      if (f.has_csg)
+        check(rt_scene_create_tree(f.shapes.data(), f.shapes.size(), f.shape_group.data(), f.shape_side.data(),
+                                   f.nodes.data(), f.nodes.size(), f.tris.data(), f.tris.size(), l.data(), l.size(),
+                                   device, &s),
+              "rt_scene_create");
+      else
+        check(rt_scene_create_mesh(f.shapes.data(), f.shapes.size(), f.shape_group.data(), f.groups.data(),
+                                   f.groups.size(), f.tris.data(), f.tris.size(), l.data(), l.size(), device, &s),
+              "rt_scene_create");
       scene_ = s;
       scene_device_ = device;
     }
@@ -567,6 +686,9 @@ class World {
   }
 
  private:
+  static const char* not_a_primitive(const GroupChild& c) {
+    return c.group ? "World::object: object is a Group" : "World::object: object is a Csg";
+  }
   void drop() {
     if (scene_) rt_scene_destroy(scene_);
     scene_ = nullptr;

@@ -92,6 +92,13 @@ extern "C" int rtamd_render_shard_host(const rt_scene* scene, const rt_camera_de
                                        uint32_t aa_samples, uint32_t row_block, uint32_t shard, uint32_t n_shards,
                                        double* out_rgb, rt_stats* stats);
 
+// a copy of a Group's, Csg's or World's child as its Python type
+static py::object child_object(const GroupChild& c) {
+  if (c.shape) return py::cast(*c.shape);
+  if (c.group) return py::cast(*c.group);
+  return py::cast(*c.csg);
+}
+
 PYBIND11_MODULE(_rtamd, m) {
   m.doc() = "MI355X-native render path of raytracer-challenge-rs (host API over the C-ABI)";
   py::register_exception<RtError>(m, "RtError");
@@ -256,6 +263,7 @@ PYBIND11_MODULE(_rtamd, m) {
       .def(py::init<>())
       .def("add_child", [](Group& g, const Shape& s) { g.add_child(s); })
       .def("add_child", [](Group& g, const Group& c) { g.add_child(c); })
+      .def("add_child", [](Group& g, const Csg& c) { g.add_child(c); })
       .def("set_transform", &Group::set_transform)
       .def("set_material", &Group::set_material)
       .def_readonly("transform", &Group::transform)
@@ -263,13 +271,44 @@ PYBIND11_MODULE(_rtamd, m) {
       .def_readonly("material", &Group::material)
       .def("n_children", [](const Group& g) { return g.children.size(); })
       .def("child", [](const Group& g, size_t i) -> py::object {
-        const GroupChild& c = g.children.at(i);
-        if (c.shape) return py::cast(*c.shape);
-        return py::cast(*c.group);
+        return child_object(g.children.at(i));
       })
       .def("get_bounds", [](const Group& g) { return g.bbox; })
       .def("parent_space_bounds", &Group::parent_space_bounds)
       .def("divide", &Group::divide, py::arg("threshold"));
+  // geometry/shape/csg.rs: children by value, as Csg::new takes them; left / right return copies
+  py::enum_<Operation>(m, "Operation")
+      .value("Union", Operation::Union).value("Intersection", Operation::Intersection)
+      .value("Difference", Operation::Difference);
+  py::class_<Csg>(m, "Csg")
+      .def(py::init([](Operation op, py::object l, py::object r) {
+        auto child = [](py::object o) -> GroupChild {
+          if (py::isinstance<Shape>(o)) return make_child(o.cast<const Shape&>());
+          if (py::isinstance<Group>(o)) return make_child(o.cast<const Group&>());
+          if (py::isinstance<Csg>(o)) return make_child(o.cast<const Csg&>());
+          throw std::invalid_argument("Csg: left / right must be a Shape, a Group or a Csg");
+        };
+        const GroupChild a = child(l), b = child(r);
+        auto with_left = [&](auto& lv) {
+          if (b.shape) return Csg(op, lv, *b.shape);
+          if (b.group) return Csg(op, lv, *b.group);
+          return Csg(op, lv, *b.csg);
+        };
+        if (a.shape) return with_left(*a.shape);
+        if (a.group) return with_left(*a.group);
+        return with_left(*a.csg);
+      }), py::arg("operation"), py::arg("left"), py::arg("right"))
+      .def_property_readonly("operation", [](const Csg& c) { return c.operation; })
+      .def_property_readonly("left", [](const Csg& c) { return child_object(c.left); })
+      .def_property_readonly("right", [](const Csg& c) { return child_object(c.right); })
+      .def("set_transform", &Csg::set_transform)
+      .def("set_material", &Csg::set_material)
+      .def_readonly("transform", &Csg::transform)
+      .def_readonly("transform_inverse", &Csg::transform_inverse)
+      .def_readonly("material", &Csg::material)
+      .def("get_bounds", [](const Csg& c) { return c.bbox; })
+      .def("parent_space_bounds", &Csg::parent_space_bounds)
+      .def("divide", &Csg::divide, py::arg("threshold"));
   // bounding_box.rs: the box type behind Group culling
   py::class_<BoundingBox>(m, "BoundingBox")
       .def(py::init<>())
@@ -378,6 +417,8 @@ PYBIND11_MODULE(_rtamd, m) {
       .def_static("default", &World::make_default)
       .def("add_object", [](World& w, const Shape& s) { w.add_object(s); })
       .def("add_object", [](World& w, const Group& g) { w.add_object(g); })
+      .def("add_object", [](World& w, const Csg& c) { w.add_object(c); })
+      .def("child", [](const World& w, size_t i) { return child_object(w.child_c(i)); })  // a copy of object i
       .def("add_light", &World::add_light)
       .def("n_objects", &World::n_objects)
       .def("n_lights", &World::n_lights)
@@ -405,6 +446,15 @@ PYBIND11_MODULE(_rtamd, m) {
         return pod_bytes(f.groups.data(), f.groups.size() * sizeof(rt_group_desc));
       })
       .def("shape_groups", [](const World& w) { return w.flatten().shape_group; })  // innermost group per shape
+      // with a Csg in the world (rt_scene_create_tree): rt_node_desc[] (groups and csgs, parents
+      // first; empty without a Csg), each shape's innermost node (shape_groups) and its side
+      .def("nodes_bytes", [](const World& w) {
+        auto f = w.flatten();
+        if (!f.has_csg) f.nodes.clear();
+        return pod_bytes(f.nodes.data(), f.nodes.size() * sizeof(rt_node_desc));
+      })
+      .def("shape_nodes", [](const World& w) { return w.flatten().shape_group; })
+      .def("shape_sides", [](const World& w) { return w.flatten().shape_side; })
       .def("triangles_bytes", [](const World& w) {  // rt_triangle_desc[], the triangles among the shapes in order
         const auto t = w.flatten().tris;
         return pod_bytes(t.data(), t.size() * sizeof(rt_triangle_desc));

@@ -220,6 +220,7 @@ int rt_abi_version(void) { return RT_ABI_VERSION; }
 size_t rt_sizeof_shape_desc(void) { return sizeof(rt_shape_desc); }
 size_t rt_sizeof_camera_desc(void) { return sizeof(rt_camera_desc); }
 size_t rt_sizeof_stats(void) { return sizeof(rt_stats); }
+size_t rt_sizeof_node_desc(void) { return sizeof(rt_node_desc); }
 static_assert(sizeof(rt_shape_desc) == 680 && sizeof(rt_camera_desc) == 160 && sizeof(rt_stats) == 112,
               "ABI struct sizes (include/rt_render.h, INTEGRATION.md)");
 

@@ -8,6 +8,7 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "rt_csg.hpp"
 #include "rt_layout.hpp"
 #include "rt_pow.hpp"
 
@@ -327,14 +328,16 @@ __device__ __forceinline__ void bbox_check_axis(double origin, double direction,
   }
   if (tmin > tmax) { t0 = tmax; t1 = tmin; } else { t0 = tmin; t1 = tmax; }
 }
-__device__ __forceinline__ bool bbox_intersects(cGroupRec g, V3 o, V3 d) {
+template <typename BP>  // BP: constant-address (wave-uniform) or generic pointer to a box's corners
+__device__ __forceinline__ bool bbox_intersects(BP lo, BP hi, V3 o, V3 d) {
   double x0, x1, y0, y1, z0, z1;
-  bbox_check_axis(o.x, d.x, g->lo[0], g->hi[0], x0, x1);
-  bbox_check_axis(o.y, d.y, g->lo[1], g->hi[1], y0, y1);
-  bbox_check_axis(o.z, d.z, g->lo[2], g->hi[2], z0, z1);
+  bbox_check_axis(o.x, d.x, lo[0], hi[0], x0, x1);
+  bbox_check_axis(o.y, d.y, lo[1], hi[1], y0, y1);
+  bbox_check_axis(o.z, d.z, lo[2], hi[2], z0, z1);
   const double tmin = fmax(fmax(x0, y0), z0), tmax = fmin(fmin(x1, y1), z1);
   return tmin <= tmax;
 }
+__device__ __forceinline__ bool bbox_intersects(cGroupRec g, V3 o, V3 d) { return bbox_intersects(g->lo, g->hi, o, d); }
 // Group::intersect (group.rs:49-58): a shape inside groups is intersected only
 // when the ray meets the box of every group around it, innermost first (the
 // reference tests them outermost first and stops at the first miss; either
@@ -352,6 +355,142 @@ struct GateSkips {
   unsigned sph = 0, plane = 0, other = 0;
 };
 
+// ------------------------------------------------------------------- Csg
+__device__ __forceinline__ void csg_skip(GateSkips& sk, int counts) {
+  sk.sph += counts & 255; sk.plane += (counts >> 8) & 255; sk.other += (counts >> 16) & 255;
+}
+// Shape::intersect (geometry/mod.rs:46-49) of one leaf under a Csg, appended to
+// the list in push order: the sphere's roots as sphere_adc forms them, the
+// plane's as plane_test, the solids' as quad_test (quad_local_intersect).
+__device__ __forceinline__ void csg_leaf(const OtherRec* q, V3 o, V3 d, CsgList& xs, unsigned& n_disc) {
+  const double* m = q->m;
+  const V3 lo = m34_point(m, o);
+  const V3 ld = v3(m[0] * d.x + m[1] * d.y + m[2] * d.z, m[4] * d.x + m[5] * d.y + m[6] * d.z,
+                   m[8] * d.x + m[9] * d.y + m[10] * d.z);
+  const int k0 = (q->meta >> 1) << kKeyShift;
+  if (q->kind == 0) {  // sphere.rs:47-62
+    const double a = ld.x * ld.x + ld.y * ld.y + ld.z * ld.z;
+    const double dt = ld.x * lo.x + ld.y * lo.y + ld.z * lo.z;
+    const double c = lo.x * lo.x + lo.y * lo.y + lo.z * lo.z - 1.0;
+    const double disc = dt * dt - a * c;
+    if (disc >= 0.0) {
+      ++n_disc;
+      const double s = sqrt(disc);
+      csg_push(xs, (-dt - s) / a, k0);
+      csg_push(xs, (-dt + s) / a, k0 + 1);
+    }
+  } else if (q->kind == 1) {  // plane.rs:53-60
+    if (!(fabs(ld.y) < kEpsilon)) csg_push(xs, -lo.y / ld.y, k0);
+  } else {
+    double t[4];
+    const int n = quad_local_intersect(q->kind, q->minimum, q->maximum, q->closed != 0, lo, ld, t);
+    for (int i = 0; i < n; ++i) csg_push(xs, t[i], k0 + i);
+  }
+}
+// A unit's surviving intersections into `h`, as quad_test folds one object's
+// list, but counted over each leaf's SURVIVORS: the nearest t >= 0 competes by
+// (t, key) (the unit's list is in key order under ties, and its leaves' object
+// indices are consecutive, so this is the world's stable sort, world.rs:31-38);
+// the hit leaf is in `containers` when an odd number of its survivors lie
+// before the origin; a leaf with an odd number of survivors t < 0 is a
+// container candidate at its last one. Shadow rays: the leaf's own has_shadow.
+template <bool SHADOW>
+__device__ __forceinline__ void csg_fold(const DevScene& sc, const CsgList& xs, Hit& h) {
+  int best = -1;
+  double bt = h.t;
+  int bk = h.key;
+  for (int i = 0; i < xs.n; ++i) {
+    const double t = xs.t[i];
+    if (t >= 0.0) {
+      if (better(t, xs.key[i], bt, bk) && (!SHADOW || sc.shade[xs.key[i] >> kKeyShift].shadow)) {
+        bt = t; bk = xs.key[i]; best = i;
+      }
+    } else if (!SHADOW && t < 0.0) {
+      const int obj = xs.key[i] >> kKeyShift;
+      int n_neg = 0;
+      bool last = true;
+      for (int j = 0; j < xs.n; ++j)
+        if ((xs.key[j] >> kKeyShift) == obj && xs.t[j] < 0.0) {
+          ++n_neg;
+          if (j > i) last = false;
+        }
+      if (last && (n_neg & 1)) push_container(h, t, xs.key[i]);
+    }
+  }
+  if (best >= 0) {
+    const int obj = bk >> kKeyShift;
+    int n_neg = 0;
+    for (int j = 0; j < xs.n; ++j)
+      if ((xs.key[j] >> kKeyShift) == obj && xs.t[j] < 0.0) ++n_neg;
+    h.t = bt; h.key = bk; h.hin = n_neg & 1;
+  }
+}
+// World::intersect's share of the Csg units (world.rs:31-38 over the Csgs of
+// World::objects, and over those inside groups, whose gates come first).
+// Per unit: the ray goes down the chain one matrix after another (never a
+// product), every gate is the reference's, in binary64; the leaves append to
+// one list, each Csg node closes its tail (rt_csg.hpp), the root's survivors
+// fold into `h`. COUNT_ONLY: the gates alone, for a counted launch's ray that
+// was answered before (count_rest_gates). Inlined like every other trace
+// function: the list, the ray stack and the list starts are private arrays
+// indexed per lane (scratch, as the walks' stacks), and nothing is reached
+// through a pointer to a local.
+template <bool SHADOW, bool COUNT_ONLY>
+__device__ __forceinline__ void csg_units(const DevScene& sc, V3 o, V3 d, Hit& h, unsigned& n_disc, GateSkips* skips) {
+  GateSkips sk;
+  unsigned disc = 0;
+  for (int u = 0; u < sc.n_csg_units; ++u) {
+    const CsgUnit un = sc.csg_units[u];
+    if (un.gate && !group_gate(sc, un.gate, o, d)) {  // Group::intersect (group.rs:49-58)
+      csg_skip(sk, un.counts);
+      continue;
+    }
+    CsgList xs;
+    xs.n = 0;
+    double ray[kCsgMaxDepth + 1][6];
+    int start[kCsgMaxDepth + 1];
+    int lvl = 0;
+    V3 co = o, cd = d;
+    const int end = un.first + un.n;
+    for (int pc = un.first; pc < end;) {
+      const CsgOp op = sc.csg_ops[pc];
+      if (op.code == kCsgEnter) {
+        const CsgRec* c = sc.csg_nodes + op.arg;
+        const V3 lo = m34_point(c->m, co);  // Ray::transform by the Csg's own inverse (ray.rs:26-28)
+        const V3 ld = v3(c->m[0] * cd.x + c->m[1] * cd.y + c->m[2] * cd.z, c->m[4] * cd.x + c->m[5] * cd.y + c->m[6] * cd.z,
+                         c->m[8] * cd.x + c->m[9] * cd.y + c->m[10] * cd.z);
+        if (lvl >= kCsgMaxDepth || !bbox_intersects(c->lo, c->hi, lo, ld)) {  // csg.rs:116-118
+          csg_skip(sk, op.counts);
+          pc = op.skip_to;
+          continue;
+        }
+        ray[lvl][0] = co.x; ray[lvl][1] = co.y; ray[lvl][2] = co.z;
+        ray[lvl][3] = cd.x; ray[lvl][4] = cd.y; ray[lvl][5] = cd.z;
+        start[lvl] = xs.n;
+        ++lvl;
+        co = lo; cd = ld;
+      } else if (op.code == kCsgExit) {
+        --lvl;
+        if (!COUNT_ONLY) csg_close(xs, start[lvl], sc.csg_nodes[op.arg].op, sc.csg_nodes[op.arg].split);
+        co = v3(ray[lvl][0], ray[lvl][1], ray[lvl][2]);
+        cd = v3(ray[lvl][3], ray[lvl][4], ray[lvl][5]);
+      } else if (op.code == kCsgGroup) {
+        if (!bbox_intersects((cGroupRec)sc.groups + op.arg, co, cd)) {  // group.rs:50-52, the ray it is handed
+          csg_skip(sk, op.counts);
+          pc = op.skip_to;
+          continue;
+        }
+      } else {
+        if (!COUNT_ONLY) csg_leaf(sc.csg_leaves + op.arg, co, cd, xs, disc);
+      }
+      ++pc;
+    }
+    if (!COUNT_ONLY) csg_fold<SHADOW>(sc, xs, h);
+  }
+  n_disc += disc;
+  if (skips) { skips->sph += sk.sph; skips->plane += sk.plane; skips->other += sk.other; }
+}
+
 // The records outside the sphere BVH (general-transform spheres, planes,
 // cubes / cylinders / cones), tested exhaustively from global memory.
 // QUADS = false compiles the solids out (kernel variants for scenes without
@@ -359,7 +498,8 @@ struct GateSkips {
 // FAST: the fast path's remainder (the records outside both hierarchies;
 // the other bounded records are traversed by other_trace).
 // TRIS: the triangles too (the kernels of scenes without solids never meet one).
-template <bool SHADOW, bool QUADS = true, bool FAST = false, bool TRIS = QUADS>
+// CSG: the Csg units too (csg_units; the same records on both paths).
+template <bool SHADOW, bool QUADS = true, bool FAST = false, bool TRIS = QUADS, bool CSG = false>
 __device__ __forceinline__ void trace_rest(const DevScene& sc, V3 o, V3 d, Hit& h, unsigned& n_disc,
                                            GateSkips* skips = nullptr) {
   cSphereGen sg = (cSphereGen)(FAST ? sc.fx_gen : sc.sph_gen);
@@ -409,14 +549,21 @@ __device__ __forceinline__ void trace_rest(const DevScene& sc, V3 o, V3 d, Hit& 
       tri_test<SHADOW>(tr + j, o, d, h);
     }
   }
+  if constexpr (CSG) csg_units<SHADOW, false>(sc, o, d, h, n_disc, skips);
 }
 
 // The group gates trace_rest<.., QUADS, true> meets, without its tests: a counted
 // launch's ray that is answered before trace_rest runs (shadow_trace's `first`)
 // still owes the reference's count of the shapes its groups kept out.
-template <bool QUADS, bool TRIS = QUADS>
+template <bool QUADS, bool TRIS = QUADS, bool CSG = false>
 __device__ __forceinline__ void count_rest_gates(const DevScene& sc, V3 o, V3 d, GateSkips& sk) {
   if (!sc.n_groups) return;
+  if constexpr (CSG) {
+    Hit none;
+    hit_init(none);
+    unsigned nd = 0;
+    csg_units<true, true>(sc, o, d, none, nd, &sk);
+  }
   cSphereGen sg = (cSphereGen)sc.fx_gen;
   for (int j = 0; j < sc.n_fx_gen; ++j)
     if (sg[j].gate && !group_gate(sc, sg[j].gate, o, d)) ++sk.sph;
@@ -466,14 +613,14 @@ __device__ __forceinline__ void diag_test(cSphereDiag r, V3 o, V3 d, Hit& h, uns
 // Generic exhaustive trace over the scene's records in global memory (scalar
 // loads): the batch entry points (rt_hit_batch, rt_is_shadowed_batch) and
 // the wavefront fallback when the trace image does not fit in LDS.
-// TRIS = false: a scene without solids or triangles (trace_rest).
-template <bool SHADOW, bool TRIS = true>
+// TRIS = false: a scene without solids or triangles (trace_rest). CSG: one with Csg units.
+template <bool SHADOW, bool TRIS = true, bool CSG = false>
 __device__ __forceinline__ void trace(const DevScene& sc, V3 o, V3 d, Hit& h, unsigned& n_disc,
                                       GateSkips* skips = nullptr) {
   hit_init(h);
   cSphereDiag sd = (cSphereDiag)sc.sph_diag;
   for (int j = 0; j < sc.n_diag; ++j) diag_test<SHADOW>(sd + j, o, d, h, n_disc);
-  trace_rest<SHADOW, true, false, TRIS>(sc, o, d, h, n_disc, skips);
+  trace_rest<SHADOW, true, false, TRIS, CSG>(sc, o, d, h, n_disc, skips);
   hit_finish(h);
 }
 

@@ -86,6 +86,41 @@ struct alignas(64) TriShade {
 };
 static_assert(sizeof(TriShade) == 192, "TriShade must stay 192 B");
 static_assert(sizeof(GroupRec) == 64, "GroupRec must stay 64 B");
+
+// ---- Csg (geometry/shape/csg.rs). A CSG with no CSG above it is one UNIT: per
+// ray its whole tree is evaluated at once (rt_device.hpp csg_units) by a small
+// program, the unit's nodes and leaves in the reference's depth-first order
+// (a CSG's left before its right). The leaves under a unit live only here.
+//   kCsgEnter  arg = the CsgRec: transform the ray by the CSG's own inverse
+//              (Shape::intersect, geometry/mod.rs:46-49), gate on its box with
+//              that local ray (csg.rs:115-118); a miss jumps to `skip_to`
+//   kCsgExit   arg = the CsgRec: sort left ++ right, filter (csg.rs:120-125),
+//              back to the enclosing ray
+//   kCsgGroup  arg = the GroupRec: Group::intersect's gate (group.rs:49-58) with
+//              the ray it is handed; a miss jumps to `skip_to`
+//   kCsgLeaf   arg = the leaf (an OtherRec: kind 0 sphere, 1 plane, 2-4 solids)
+// `counts`: the leaves below the node by counter class, sphere | plane << 8 |
+// other << 16 (a failed gate owes the reference's count of them, GateSkips).
+enum { kCsgEnter = 0, kCsgExit = 1, kCsgGroup = 2, kCsgLeaf = 3 };
+struct alignas(16) CsgOp {
+  int32_t code, arg, skip_to, counts;
+};
+// One Csg node: transform_inverse rows 0..2, get_bounds() as local_intersect
+// tests it, the operation (csg.rs:14-19) and `split`, the first object index of
+// its right child: an intersection's object is in `left` (Shape::includes,
+// geometry/mod.rs:87-89, group.rs:104-106, csg.rs:132-134) iff its index is below.
+struct alignas(64) CsgRec {
+  double m[12];
+  double lo[3], hi[3];
+  int32_t op, split;
+  int64_t pad[5];
+};
+static_assert(sizeof(CsgRec) == 192, "CsgRec must stay 192 B");
+// One unit: its program ops[first .. first + n), the gate of the groups around it
+// (as a record's `gate`), and its leaves by counter class (as CsgOp::counts).
+struct alignas(16) CsgUnit {
+  int32_t first, n, gate, counts;
+};
 static_assert(sizeof(QuadRec) == 128, "QuadRec must stay 128 B");
 
 // Bounding-volume hierarchies (built on the host, rt_bvh.cpp): one over the
@@ -310,6 +345,13 @@ struct DevScene {
   const TriRec* trec;
   const TriRec* fx_tris;
   int32_t n_tris, n_tbvh, n_trec, n_fx_tris, tbvh_depth, pad_tris;
+  // Csg (rt_scene_create_tree): the units, their programs, nodes and leaves (csg_units), and
+  // the leaves by counter class (the reference's shape tests of a ray count them too)
+  const CsgUnit* csg_units;
+  const CsgOp* csg_ops;
+  const CsgRec* csg_nodes;
+  const OtherRec* csg_leaves;
+  int32_t n_csg_units, n_csg_sph, n_csg_planes, n_csg_other;
 };
 
 constexpr int32_t kOwnOutside = 0x40000000, kOwnIndex = 0x3FFFFFFF;  // DevScene::obj_diag

@@ -1,8 +1,11 @@
-// rt_scene.cpp — rt_scene_create / rt_scene_create_groups / rt_scene_create_mesh / rt_scene_destroy:
+// rt_scene.cpp — rt_scene_create / _groups / _mesh / _tree / rt_scene_destroy:
 // the reference's World (world.rs:18-21, shape/group.rs) flattened into SoA
 // records in the reference's object order, the exact-culling hierarchies
 // (rt_bvh.cpp), the light buffer, and one upload to the scene's device.
+#include <functional>
+
 #include "rt_api_internal.hpp"
+#include "rt_csg.hpp"
 #include "rt_wf_plan.hpp"
 
 using namespace rtapi;
@@ -107,6 +110,7 @@ int rt_scene_create_groups(const rt_shape_desc* shapes, size_t n_shapes, const i
   return rt_scene_create_mesh(shapes, n_shapes, shape_group, groups, n_groups, nullptr, 0, lights, n_lights, device, out);
 }
 
+// rt_scene_create_groups / _mesh: the tree whose nodes are all Groups.
 int rt_scene_create_mesh(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* shape_group,
                          const rt_group_desc* groups, size_t n_groups, const rt_triangle_desc* tri_descs, size_t n_tris,
                          const rt_light_desc* lights, size_t n_lights, int device, rt_scene** out) {
@@ -115,17 +119,66 @@ int rt_scene_create_mesh(const rt_shape_desc* shapes, size_t n_shapes, const int
       (n_tris && !tri_descs))
     return fail(RT_ERR_INVALID_ARGUMENT, "null pointer");
   *out = nullptr;
-  if (n_shapes > (size_t)(1u << 29)) return fail(RT_ERR_INVALID_ARGUMENT, "too many shapes");
   if (n_groups > (size_t)(1u << 24)) return fail(RT_ERR_INVALID_ARGUMENT, "too many groups");
   for (size_t g = 0; g < n_groups; ++g)
     if (groups[g].parent < -1 || groups[g].parent >= (int32_t)g)
       return fail(RT_ERR_INVALID_ARGUMENT, "group " + std::to_string(g) + ": its parent must be -1 or an earlier group");
-  // a shape's gate: 1 + its innermost group (0: none)
-  // (range-checked before the + 1: a caller's INT32_MAX must not overflow)
-  for (size_t i = 0; shape_group && n_groups && i < n_shapes; ++i)
+  for (size_t i = 0; n_groups && i < n_shapes; ++i)
     if (shape_group[i] < -1 || (int64_t)shape_group[i] >= (int64_t)n_groups)
       return fail(RT_ERR_INVALID_ARGUMENT, "shape " + std::to_string(i) + ": bad group index");
-  auto gate_of = [&](size_t i) -> int32_t { return shape_group && n_groups ? shape_group[i] + 1 : 0; };
+  std::vector<rt_node_desc> nodes(n_groups);
+  for (size_t g = 0; g < n_groups; ++g) {
+    nodes[g] = rt_node_desc{};
+    nodes[g].kind = RT_NODE_GROUP;
+    nodes[g].parent = groups[g].parent;
+    for (int c = 0; c < 3; ++c) { nodes[g].min[c] = groups[g].min[c]; nodes[g].max[c] = groups[g].max[c]; }
+  }
+  return rt_scene_create_tree(shapes, n_shapes, shape_group, nullptr, nodes.data(), n_groups, tri_descs, n_tris, lights,
+                              n_lights, device, out);
+  });
+}
+
+int rt_scene_create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* shape_node,
+                         const int32_t* shape_side, const rt_node_desc* nodes, size_t n_nodes,
+                         const rt_triangle_desc* tri_descs, size_t n_tris, const rt_light_desc* lights, size_t n_lights,
+                         int device, rt_scene** out) {
+  return guarded([&]() -> int {
+  if (!out || (n_shapes && !shapes) || (n_lights && !lights) || (n_nodes && (!nodes || !shape_node)) ||
+      (n_tris && !tri_descs))
+    return fail(RT_ERR_INVALID_ARGUMENT, "null pointer");
+  *out = nullptr;
+  if (n_shapes > (size_t)(1u << 29)) return fail(RT_ERR_INVALID_ARGUMENT, "too many shapes");
+  if (n_nodes > (size_t)(1u << 24)) return fail(RT_ERR_INVALID_ARGUMENT, "too many nodes");
+  for (size_t g = 0; g < n_nodes; ++g)
+    if (nodes[g].parent < -1 || nodes[g].parent >= (int32_t)g)
+      return fail(RT_ERR_INVALID_ARGUMENT, "node " + std::to_string(g) + ": its parent must be -1 or an earlier node");
+  // ---- Csg nodes: each node's unit (the outermost Csg at or above it, -1: none) and the
+  // Csg nodes from that unit down to it
+  std::vector<int32_t> unit_of_node(n_nodes, -1), csg_level(n_nodes, 0);
+  bool any_csg = false;
+  for (size_t g = 0; g < n_nodes; ++g) {
+    const rt_node_desc& nd = nodes[g];
+    if (nd.kind != RT_NODE_GROUP && nd.kind != RT_NODE_CSG)
+      return fail(RT_ERR_INVALID_ARGUMENT, "node " + std::to_string(g) + ": bad kind");
+    const bool csg = nd.kind == RT_NODE_CSG;
+    if (csg && (nd.operation < RT_CSG_UNION || nd.operation > RT_CSG_DIFFERENCE))
+      return fail(RT_ERR_INVALID_ARGUMENT, "node " + std::to_string(g) + ": bad Csg operation");
+    if (nd.parent >= 0 && nodes[nd.parent].kind == RT_NODE_CSG && nd.side != 0 && nd.side != 1)
+      return fail(RT_ERR_INVALID_ARGUMENT, "node " + std::to_string(g) + ": side must be 0 (left) or 1 (right)");
+    const int32_t up = nd.parent >= 0 ? unit_of_node[(size_t)nd.parent] : -1;
+    unit_of_node[g] = up >= 0 ? up : (csg ? (int32_t)g : -1);
+    csg_level[g] = (up >= 0 ? csg_level[(size_t)nd.parent] : 0) + (csg ? 1 : 0);
+    any_csg = any_csg || csg;
+    if (csg_level[g] > kCsgMaxDepth)
+      return fail(RT_ERR_UNSUPPORTED_SHAPE, "node " + std::to_string(g) + ": more than RT_CSG_MAX_DEPTH = " +
+                                                std::to_string(kCsgMaxDepth) + " nested Csg nodes");
+  }
+  // a shape's gate: 1 + its innermost group (0: none)
+  // (range-checked before the + 1: a caller's INT32_MAX must not overflow)
+  for (size_t i = 0; shape_node && n_nodes && i < n_shapes; ++i)
+    if (shape_node[i] < -1 || (int64_t)shape_node[i] >= (int64_t)n_nodes)
+      return fail(RT_ERR_INVALID_ARGUMENT, "shape " + std::to_string(i) + ": bad node index");
+  auto gate_of = [&](size_t i) -> int32_t { return shape_node && n_nodes ? shape_node[i] + 1 : 0; };
   for (size_t i = 0; i < n_shapes; ++i) {
     // (without vertex data, rt_scene_create / rt_scene_create_groups: no triangles)
     if (shapes[i].kind < RT_SHAPE_SPHERE || shapes[i].kind > (n_tris ? RT_SHAPE_SMOOTH_TRIANGLE : RT_SHAPE_CONE))
@@ -134,6 +187,25 @@ int rt_scene_create_mesh(const rt_shape_desc* shapes, size_t n_shapes, const int
                                                 (n_tris ? ", Triangle, SmoothTriangle" : ""));
     if (shapes[i].pattern_kind < RT_PATTERN_NONE || shapes[i].pattern_kind > RT_PATTERN_CHECKERS)
       return fail(RT_ERR_INVALID_ARGUMENT, "shape " + std::to_string(i) + ": bad pattern kind");
+  }
+  // a shape under a Csg: a leaf of that Csg's unit (kinds 0-4 only)
+  std::vector<int32_t> unit_of(n_shapes, -1);
+  if (any_csg) {
+    std::vector<int32_t> n_leaves(n_nodes, 0);
+    for (size_t i = 0; i < n_shapes; ++i) {
+      const int32_t nd = shape_node[i];
+      if (nd < 0) continue;
+      if (nodes[nd].kind == RT_NODE_CSG && (!shape_side || (shape_side[i] != 0 && shape_side[i] != 1)))
+        return fail(RT_ERR_INVALID_ARGUMENT, "shape " + std::to_string(i) + ": side must be 0 (left) or 1 (right)");
+      const int32_t u = unit_of_node[(size_t)nd];
+      if (u < 0) continue;
+      unit_of[i] = u;
+      if (shapes[i].kind > RT_SHAPE_CONE)
+        return fail(RT_ERR_UNSUPPORTED_SHAPE, "shape " + std::to_string(i) + ": a Triangle under a Csg is not supported");
+      if (++n_leaves[(size_t)u] > kCsgMaxLeaves)
+        return fail(RT_ERR_UNSUPPORTED_SHAPE, "node " + std::to_string(u) + ": more than RT_CSG_MAX_LEAVES = " +
+                                                  std::to_string(kCsgMaxLeaves) + " primitives under one Csg");
+    }
   }
   // the j-th triangle shape takes tri_descs[j]
   std::vector<const rt_triangle_desc*> tri_of;
@@ -166,11 +238,25 @@ int rt_scene_create_mesh(const rt_shape_desc* shapes, size_t n_shapes, const int
   std::vector<TriRec> tris;
   std::vector<TriShade> tri_shade;
   std::vector<ShadeRec> shade(n_shapes);
+  std::vector<OtherRec> csg_leaves;  // the leaves under Csg units live only here
+  std::vector<int32_t> leaf_of(n_shapes, -1);
+  int32_t n_csg_kind[3] = {0, 0, 0};  // by counter class: spheres, planes, others
   for (size_t i = 0; i < n_shapes; ++i) {
     const rt_shape_desc& d = shapes[i];
     const int64_t meta = ((int64_t)i << 1) | (d.casts_shadow ? 1 : 0);
     const int32_t gate = gate_of(i);  // shapes inside groups: general records with their group gate
-    if (d.kind == RT_SHAPE_SPHERE) {
+    if (unit_of[i] >= 0) {  // its gates are the unit's program's (csg_units)
+      OtherRec r{};
+      for (int e = 0; e < 12; ++e) r.m[e] = d.inverse[e];
+      r.minimum = d.minimum;
+      r.maximum = d.maximum;
+      r.kind = d.kind;
+      r.closed = d.closed ? 1 : 0;
+      r.meta = (int32_t)meta;
+      leaf_of[i] = (int32_t)csg_leaves.size();
+      csg_leaves.push_back(r);
+      ++n_csg_kind[d.kind == RT_SHAPE_SPHERE ? 0 : d.kind == RT_SHAPE_PLANE ? 1 : 2];
+    } else if (d.kind == RT_SHAPE_SPHERE) {
       if (is_diag_inverse(d.inverse) && gate == 0) {
         SphereDiag r{};
         r.s[0] = d.inverse[0]; r.s[1] = d.inverse[5]; r.s[2] = d.inverse[10];
@@ -275,10 +361,87 @@ int rt_scene_create_mesh(const rt_shape_desc* shapes, size_t n_shapes, const int
     else if (q.gate == 0 && line_box(q, blo, bhi)) line_rec.push_back(q);  // (grouped tubes and cones: exhaustive)
     else fx_quads.push_back(q);
   }
-  std::vector<GroupRec> grec(n_groups);
-  for (size_t g = 0; g < n_groups; ++g) {
-    for (int c = 0; c < 3; ++c) { grec[g].lo[c] = groups[g].min[c]; grec[g].hi[c] = groups[g].max[c]; }
-    grec[g].parent = groups[g].parent + 1;
+  // ---- the Csg units' programs (rt_layout.hpp CsgOp), nodes and leaves depth first
+  std::vector<CsgUnit> csg_units;
+  std::vector<CsgOp> csg_ops;
+  std::vector<CsgRec> csg_nodes;
+  if (any_csg) {
+    // a node's children: sub-nodes and shapes, by the first shape below them (the shapes come depth first)
+    struct Child { int32_t first, side, node, shape; };
+    std::vector<std::vector<Child>> kids(n_nodes);
+    std::vector<int32_t> first_shape(n_nodes, INT32_MAX);
+    for (size_t i = n_shapes; i-- > 0;) {
+      for (int32_t g = shape_node[i]; g >= 0; g = nodes[g].parent) first_shape[(size_t)g] = (int32_t)i;
+    }
+    for (size_t i = 0; i < n_shapes; ++i)
+      if (unit_of[i] >= 0) kids[(size_t)shape_node[i]].push_back(Child{(int32_t)i, shape_side ? shape_side[i] : 0, -1, (int32_t)i});
+    for (size_t g = 0; g < n_nodes; ++g)
+      if (unit_of_node[g] >= 0 && unit_of_node[g] != (int32_t)g)
+        kids[(size_t)nodes[g].parent].push_back(Child{first_shape[g], nodes[g].side, (int32_t)g, -1});
+    for (auto& k : kids) std::stable_sort(k.begin(), k.end(), [](const Child& a, const Child& b) { return a.first < b.first; });
+    auto pack = [](const int32_t* c) { return c[0] | c[1] << 8 | c[2] << 16; };
+    int32_t next_shape = 0;
+    bool in_order = true, two_sided = true;
+    // emits the node's subtree; cnt: its leaves by counter class
+    std::function<void(int32_t, int32_t*)> emit = [&](int32_t g, int32_t* cnt) {
+      const rt_node_desc& nd = nodes[g];
+      const size_t at = csg_ops.size();
+      const bool csg = nd.kind == RT_NODE_CSG;
+      const int32_t rec = (int32_t)csg_nodes.size();
+      if (csg) {
+        CsgRec r{};
+        for (int e = 0; e < 12; ++e) r.m[e] = nd.inverse[e];
+        for (int c = 0; c < 3; ++c) { r.lo[c] = nd.min[c]; r.hi[c] = nd.max[c]; }
+        r.op = nd.operation;
+        csg_nodes.push_back(r);
+      }
+      csg_ops.push_back(CsgOp{csg ? kCsgEnter : kCsgGroup, csg ? rec : g, 0, 0});
+      int32_t mine[3] = {0, 0, 0};
+      int n_side[2] = {0, 0};
+      for (int pass = 0; pass < (csg ? 2 : 1); ++pass) {
+        if (csg && pass == 1) csg_nodes[(size_t)rec].split = next_shape;  // the right child's first object
+        for (const Child& c : kids[(size_t)g]) {
+          if (csg && c.side != pass) continue;
+          ++n_side[pass];
+          if (c.node >= 0) {
+            emit(c.node, mine);
+          } else {
+            in_order = in_order && c.shape == next_shape;
+            next_shape = c.shape + 1;
+            const int k = shapes[c.shape].kind;
+            ++mine[k == RT_SHAPE_SPHERE ? 0 : k == RT_SHAPE_PLANE ? 1 : 2];
+            csg_ops.push_back(CsgOp{kCsgLeaf, leaf_of[(size_t)c.shape], 0, 0});
+          }
+        }
+      }
+      if (csg) {
+        two_sided = two_sided && n_side[0] == 1 && n_side[1] == 1;
+        csg_ops.push_back(CsgOp{kCsgExit, rec, 0, 0});
+      }
+      csg_ops[at].skip_to = (int32_t)csg_ops.size();
+      csg_ops[at].counts = pack(mine);
+      for (int c = 0; c < 3; ++c) cnt[c] += mine[c];
+    };
+    for (size_t g = 0; g < n_nodes; ++g) {
+      if (unit_of_node[g] != (int32_t)g) continue;
+      CsgUnit u{};
+      u.first = (int32_t)csg_ops.size();
+      u.gate = nodes[g].parent + 1;
+      int32_t cnt[3] = {0, 0, 0};
+      next_shape = first_shape[g] == INT32_MAX ? 0 : first_shape[g];
+      emit((int32_t)g, cnt);
+      u.n = (int32_t)csg_ops.size() - u.first;
+      u.counts = pack(cnt);
+      csg_units.push_back(u);
+    }
+    if (!two_sided) return fail(RT_ERR_INVALID_ARGUMENT, "a Csg node needs exactly one left and one right child");
+    if (!in_order)
+      return fail(RT_ERR_INVALID_ARGUMENT, "the shapes under a Csg are not in depth-first order (left before right)");
+  }
+  std::vector<GroupRec> grec(n_nodes);
+  for (size_t g = 0; g < n_nodes; ++g) {
+    for (int c = 0; c < 3; ++c) { grec[g].lo[c] = nodes[g].min[c]; grec[g].hi[c] = nodes[g].max[c]; }
+    grec[g].parent = nodes[g].parent + 1;
   }
   // A handful of records is cheaper in the exhaustive loops (wave-uniform, scalar loads) than
   // behind a per-lane walk from global memory: the hierarchies start at kMinHierRecords
@@ -378,7 +541,11 @@ int rt_scene_create_mesh(const rt_shape_desc* shapes, size_t n_shapes, const int
   const size_t o_tb = align(o_ts + (tri_shade.size() + 1) * sizeof(TriShade));
   const size_t o_tl = align(o_tb + (tbvh.size() + 1) * sizeof(BvhNode));
   const size_t o_tx = align(o_tl + (trec.size() + 1) * sizeof(TriRec));
-  const size_t total = align(o_tx + (fx_tris.size() + 1) * sizeof(TriRec)) + 256;
+  const size_t o_cu = align(o_tx + (fx_tris.size() + 1) * sizeof(TriRec));
+  const size_t o_co = align(o_cu + (csg_units.size() + 1) * sizeof(CsgUnit));
+  const size_t o_cn = align(o_co + (csg_ops.size() + 1) * sizeof(CsgOp));
+  const size_t o_cl = align(o_cn + (csg_nodes.size() + 1) * sizeof(CsgRec));
+  const size_t total = align(o_cl + (csg_leaves.size() + 1) * sizeof(OtherRec)) + 256;
   std::vector<unsigned char> host(total, 0);
   if (!diag.empty()) std::memcpy(&host[o_diag], diag.data(), diag.size() * sizeof(SphereDiag));
   if (!gen.empty()) std::memcpy(&host[o_gen], gen.data(), gen.size() * sizeof(SphereGen));
@@ -427,6 +594,10 @@ int rt_scene_create_mesh(const rt_shape_desc* shapes, size_t n_shapes, const int
   if (!tbvh.empty()) std::memcpy(&host[o_tb], tbvh.data(), tbvh.size() * sizeof(BvhNode));
   if (!trec.empty()) std::memcpy(&host[o_tl], trec.data(), trec.size() * sizeof(TriRec));
   if (!fx_tris.empty()) std::memcpy(&host[o_tx], fx_tris.data(), fx_tris.size() * sizeof(TriRec));
+  if (!csg_units.empty()) std::memcpy(&host[o_cu], csg_units.data(), csg_units.size() * sizeof(CsgUnit));
+  if (!csg_ops.empty()) std::memcpy(&host[o_co], csg_ops.data(), csg_ops.size() * sizeof(CsgOp));
+  if (!csg_nodes.empty()) std::memcpy(&host[o_cn], csg_nodes.data(), csg_nodes.size() * sizeof(CsgRec));
+  if (!csg_leaves.empty()) std::memcpy(&host[o_cl], csg_leaves.data(), csg_leaves.size() * sizeof(OtherRec));
   if (!lb.cells.empty()) {
     std::memcpy(&host[o_lc], lb.cells.data(), lb.cells.size() * sizeof(LbCell));
     if (!lb.ov.empty()) std::memcpy(&host[o_lv], lb.ov.data(), lb.ov.size() * sizeof(uint16_t));
@@ -501,7 +672,7 @@ int rt_scene_create_mesh(const rt_shape_desc* shapes, size_t n_shapes, const int
   s->dev.obj_diag = (const int32_t*)(b + o_od);
   s->dev.lights = (const LightRec*)(b + o_li);
   s->dev.groups = (const GroupRec*)(b + o_gr);
-  s->dev.n_groups = (int32_t)n_groups;
+  s->dev.n_groups = (int32_t)n_nodes;
   s->dev.tris = (const TriRec*)(b + o_tr);
   s->dev.tri_shade = (const TriShade*)(b + o_ts);
   s->dev.tbvh = tbvh.empty() ? nullptr : (const BvhNode*)(b + o_tb);
@@ -512,6 +683,14 @@ int rt_scene_create_mesh(const rt_shape_desc* shapes, size_t n_shapes, const int
   s->dev.n_trec = (int32_t)trec.size();
   s->dev.n_fx_tris = (int32_t)fx_tris.size();
   s->dev.tbvh_depth = tbvh_depth;
+  s->dev.csg_units = (const CsgUnit*)(b + o_cu);
+  s->dev.csg_ops = (const CsgOp*)(b + o_co);
+  s->dev.csg_nodes = (const CsgRec*)(b + o_cn);
+  s->dev.csg_leaves = (const OtherRec*)(b + o_cl);
+  s->dev.n_csg_units = (int32_t)csg_units.size();
+  s->dev.n_csg_sph = n_csg_kind[0];
+  s->dev.n_csg_planes = n_csg_kind[1];
+  s->dev.n_csg_other = n_csg_kind[2];
   s->dev.n_diag = (int32_t)diag.size();
   s->dev.n_gen = (int32_t)gen.size();
   s->dev.n_planes = (int32_t)planes.size();

@@ -750,3 +750,119 @@ def mesh_scene(width=640, height=360, nu=64, nv=64, smooth=True, divide=5, seed=
     w.add_light(rt.PointLight(rt.Point(-6.0, 8.0, -8.0), rt.Color(0.8, 0.8, 0.8)))
     w.add_light(rt.PointLight(rt.Point(5.0, 6.0, -3.0), rt.Color(0.4, 0.4, 0.5)))
     return text, w, _camera(width, height, PI / 3.0, (0.0, 2.6, -6.0), (0.0, 0.9, 0.0)), depth
+
+
+# ---- Csg (geometry/shape/csg.rs). A Csg's own transform is left at the identity in these
+# scenes and the placement goes into the leaves: the reference tests a Csg's box, which is in
+# the Csg's parent space, against the ray in the Csg's local space (csg.rs:115-118), so a
+# transformed Csg is culled by the wrong box (tests/test_gpu_csg.py renders that quirk too).
+def csg_die(place, material, hole=0.35):
+    """(cube ∩ sphere) − (three cylinders along x, y, z), built by nesting; `place` moves every leaf."""
+    cube = rt.Cube()
+    cube.set_transform(place)
+    ball = rt.Sphere()
+    ball.set_transform(place * rt.scaling(1.38, 1.38, 1.38))
+    cube.set_material(material)
+    ball.set_material(material)
+    body = rt.Csg(rt.Operation.Intersection, cube, ball)
+    drills = []
+    for turn in (rt.rotation_z(PI / 2.0), None, rt.rotation_x(PI / 2.0)):
+        c = rt.Cylinder(-1.5, 1.5, True)
+        c.set_transform((place * turn if turn is not None else place) * rt.scaling(hole, 1.0, hole))
+        c.set_material(material)
+        drills.append(c)
+    holes = rt.Csg(rt.Operation.Union, drills[0], rt.Csg(rt.Operation.Union, drills[1], drills[2]))
+    return rt.Csg(rt.Operation.Difference, body, holes)
+
+
+def csg_dice(n=16, width=640, height=360, seed=0x5EED0C56, depth=5):
+    """`n` drilled dice on a reflective floor, every third of glass and every third a mirror, two
+    lights. A die is a Csg of five leaves and four nodes (three levels)."""
+    rng = SplitMix64(seed)
+    w = rt.World()
+    floor = rt.Plane()
+    floor.material.color = rt.Color(0.8, 0.8, 0.85)
+    floor.material.reflective = 0.2
+    floor.material.specular = 0.0
+    w.add_object(floor)
+    side = max(1, int(math.ceil(math.sqrt(n))))
+    for k in range(n):
+        gx, gz = k % side, k // side
+        s = 0.35 + 0.15 * rng.u()
+        place = (rt.translation(1.6 * (gx - (side - 1) / 2.0) + 0.3 * (rng.u() - 0.5), s,
+                                1.6 * gz + 0.3 * (rng.u() - 0.5))
+                 * rt.rotation_y(PI * rng.u()) * rt.scaling(s, s, s))
+        m = rt.Material()
+        m.color = rt.Color(0.2 + 0.8 * rng.u(), 0.2 + 0.8 * rng.u(), 0.2 + 0.8 * rng.u())
+        if k % 3 == 1:  # glass
+            m.color = rt.Color(0.05, 0.05, 0.1)
+            m.diffuse, m.transparency, m.reflective = 0.1, 0.9, 0.5
+            m.refractive_index = 1.3 + 0.4 * rng.u()
+        elif k % 3 == 2:  # mirror
+            m.reflective = 0.6
+        w.add_object(csg_die(place, m))
+    w.add_light(rt.PointLight(rt.Point(-6, 9, -8), rt.Color(1.0, 1.0, 1.0)))
+    w.add_light(rt.PointLight(rt.Point(7, 6, -3), rt.Color(0.35, 0.35, 0.35)))
+    reach = 0.8 * side
+    return w, _camera(width, height, PI / 3.0, (0.0, 1.2 + 0.9 * reach, -2.5 - 1.2 * reach), (0, 0.3, 0.8 * reach)), depth
+
+
+def csg_random(seed, width=24, height=16):
+    """A seeded random Csg scene: a floor, two plain glass spheres, and two or three Csg trees of
+    random operations and depth (up to 3 levels) over spheres, cubes, closed cylinders and closed
+    cones with random transforms and materials; one tree sits in a group."""
+    rng = SplitMix64(0xC5600000 ^ seed)
+    w = rt.World()
+    floor = rt.Plane()
+    floor.set_transform(rt.translation(0, -1.2, 0))
+    floor.material.color = rt.Color(0.7, 0.7, 0.6)
+    floor.material.reflective = 0.25 * rng.u()
+    w.add_object(floor)
+    for k in range(2):
+        s = rt.glass_sphere()
+        r = 0.3 + 0.3 * rng.u()
+        s.set_transform(rt.translation(-2.4 + 4.8 * k + 0.4 * rng.u(), -0.4 + rng.u(), 1.0 * rng.u()) * rt.scaling(r, r, r))
+        s.material.refractive_index = 1.2 + 0.6 * rng.u()
+        s.material.reflective = 0.3
+        w.add_object(s)
+
+    def leaf(cx, cz):
+        kind = int(rng.u() * 4)
+        s = (rt.Sphere(), rt.Cube(), rt.Cylinder(-1.0, 1.0, True), rt.Cone(-1.0, 0.0, True))[kind]
+        sc = [0.45 + 0.5 * rng.u() for _ in range(3)]
+        s.set_transform(rt.translation(cx + 0.7 * (rng.u() - 0.5), 0.7 * (rng.u() - 0.5), cz + 0.7 * (rng.u() - 0.5))
+                        * rt.rotation_y(PI * rng.u()) * rt.rotation_x(PI * rng.u()) * rt.scaling(*sc))
+        s.material.color = rt.Color(rng.u(), rng.u(), rng.u())
+        style = rng.u()
+        if style < 0.35:
+            s.material.transparency = 0.5 + 0.5 * rng.u()
+            s.material.refractive_index = 1.1 + 0.9 * rng.u()
+            s.material.reflective = 0.5 * rng.u()
+            s.material.diffuse = 0.3
+        elif style < 0.55:
+            s.material.reflective = 0.2 + 0.6 * rng.u()
+        if rng.u() < 0.15:
+            s.no_shadow()
+        return s
+
+    def tree(level, cx, cz):
+        op = (rt.Operation.Union, rt.Operation.Intersection, rt.Operation.Difference)[int(rng.u() * 3)]
+        sides = []
+        for _ in range(2):
+            sides.append(tree(level - 1, cx, cz) if level > 1 and rng.u() < 0.6 else leaf(cx, cz))
+        return rt.Csg(op, sides[0], sides[1])
+
+    n_trees = 2 + int(rng.u() * 2)
+    for k in range(n_trees):
+        cx = 2.2 * (k - (n_trees - 1) / 2.0)
+        t = tree(1 + int(rng.u() * 3), cx, 0.5)
+        if k == 1:
+            g = rt.Group()
+            g.add_child(t)
+            g.add_child(leaf(cx, 2.5))
+            w.add_object(g)
+        else:
+            w.add_object(t)
+    w.add_light(rt.PointLight(rt.Point(-5, 8, -7), rt.Color(0.9, 0.9, 0.9)))
+    w.add_light(rt.PointLight(rt.Point(6, 5, -4), rt.Color(0.4, 0.4, 0.4)))
+    return w, _camera(width, height, PI / 3.0, (0.0, 1.5, -6.0), (0, 0.0, 0.5)), 4
