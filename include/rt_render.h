@@ -22,7 +22,7 @@
  *   - Every entry point may be called from any host thread, on one scene or
  *     on several at once. An rt_scene's lock is held only while a call
  *     enqueues its work: the synchronous entry points (the host-buffer calls
- *     rt_render*, rt_render_ppm, rt_color_at_batch*, rt_is_shadowed_batch,
+ *     rt_render*, rt_render_ppm, rt_render_png, rt_color_at_batch*, rt_is_shadowed_batch,
  *     rt_hit_batch, and any call given a non-NULL `stats`) wait for the device
  *     and copy their results without it, each in a context (stream, device
  *     buffers) of its own, so threads rendering one scene overlap on the GPU.
@@ -463,6 +463,48 @@ int rt_render_ppm(const rt_scene* scene, const rt_camera_desc* camera,
 
 /* `scale_color_component` (image/ppm.rs:73-75) over n values. */
 int rt_quantize_u8(const double* values, size_t n, uint8_t* out);
+
+/* ---- output (image/png.rs) ------------------------------------------------ */
+
+/* What `Canvas::save` writes (canvas.rs:23,50-52: the canvas's exporter is
+ * `PngExporter`, image/png.rs:13-31) and what `SceneParser::render` saves
+ * (scene-parser/src/lib.rs:267-284): an 8-bit RGB PNG of the canvas quantised
+ * by `(v*255).round() as u8` (png.rs:29-31, the rule of ppm.rs:73-75). The
+ * reference's bytes come from a third-party encoder; the decoded image is what
+ * it defines, and that is equal. This writer's zlib stream holds stored blocks,
+ * so the file is 63 + 5n + R bytes, R = height * (3 * width + 1) raw bytes in
+ * n = ceil(R / 65535) blocks, whatever the pixels (DESIGN.md "Output: PNG").
+ * rt_png_size returns that length, or 0 for a canvas a PNG cannot hold: width
+ * or height 0, or an IDAT payload (6 + 5n + R) above 2^31 - 1 bytes. The three
+ * encoders below refuse such a canvas with RT_ERR_INVALID_ARGUMENT. */
+size_t rt_png_size(uint32_t width, uint32_t height);
+
+/* `PngExporter::export` (image/png.rs:13-31) of a host canvas into `out` (cap
+ * bytes). Buffer conventions of rt_canvas_to_ppm: *out_len receives the file's
+ * length; out == NULL asks for it alone; a too-small cap returns
+ * RT_ERR_BUFFER_TOO_SMALL. */
+int rt_canvas_to_png(const double* rgb, uint32_t width, uint32_t height,
+                     uint8_t* out, size_t cap, size_t* out_len);
+
+/* `PngExporter::export` (image/png.rs:13-31) of a DEVICE canvas (as
+ * rt_render_shard_device writes it) into DEVICE memory `d_out` (cap bytes), on
+ * `stream` (NULL = the default stream): one pass over the canvas writes every
+ * file byte at its final offset, a second small kernel the two checksums. The
+ * bytes are those rt_canvas_to_png writes. d_out == NULL: the length only.
+ * Returns after the file is complete. */
+int rt_canvas_to_png_device(const double* d_rgb, uint32_t width, uint32_t height,
+                            uint8_t* d_out, size_t cap, size_t* out_len, void* stream);
+
+/* `camera.render(&world).save(path)`'s bytes (camera.rs:133-148, canvas.rs:50-52,
+ * image/png.rs:13-31; what scene-parser/src/lib.rs:267-284 writes) in one call:
+ * the frame is rendered, encoded on the device on the same stream, and only
+ * the file crosses to the host buffer `out` (cap bytes, pinned or pageable).
+ * *out_len receives rt_png_size(hsize, vsize); out == NULL asks for it alone
+ * (nothing is rendered), and a too-small cap returns RT_ERR_BUFFER_TOO_SMALL
+ * before anything is rendered. */
+int rt_render_png(const rt_scene* scene, const rt_camera_desc* camera,
+                  uint32_t max_depth, uint32_t aa_samples, uint8_t* out, size_t cap,
+                  size_t* out_len, rt_stats* stats);
 
 /* ---- host buffers ------------------------------------------------------------ */
 

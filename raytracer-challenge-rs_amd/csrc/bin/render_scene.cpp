@@ -1,7 +1,8 @@
 // render_scene — the reference's scene-parser/src/bin/render_scene.rs on the
 // MI355X path: `render_scene <scene-file> <output-file>` parses the YAML scene
 // (csrc/host/scene_parser.hpp) and renders it with Camera::render through the
-// C-ABI (GPU). The output is a P3 PPM (the reference writes a PNG).
+// C-ABI (GPU). An output path ending in .png gets a PNG, as the reference writes; any
+// other path gets the P3 PPM (SceneParser::render_to).
 #include <cstdio>
 #include <exception>
 

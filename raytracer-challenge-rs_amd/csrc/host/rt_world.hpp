@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <fstream>
 #include <limits>
 #include <memory>
 #include <stdexcept>
@@ -425,7 +426,7 @@ inline bool child_includes(const GroupChild& c, const Shape* s) {
   return false;
 }
 
-// canvas.rs:8-52 + image/ppm.rs
+// canvas.rs:8-52 + image/ppm.rs + image/png.rs
 // Pixel storage of a Canvas. Frames of 2 MiB and more sit on 2-MiB aligned
 // memory marked for transparent huge pages, so the first touch of a fresh
 // 50-MB canvas (the device-to-host copy of `render`) takes tens of page
@@ -493,6 +494,20 @@ class Canvas {
     check(rt_canvas_to_ppm(px_.get(), (uint32_t)w_, (uint32_t)h_, &s[0], s.size(), &len), "rt_canvas_to_ppm");
     s.resize(len);
     return s;
+  }
+  std::string to_png() const {  // PngExporter::export (image/png.rs:13-31)
+    size_t len = 0;
+    std::string s(rt_png_size((uint32_t)w_, (uint32_t)h_), '\0');
+    check(rt_canvas_to_png(px_.get(), (uint32_t)w_, (uint32_t)h_, (uint8_t*)&s[0], s.size(), &len), "rt_canvas_to_png");
+    s.resize(len);
+    return s;
+  }
+  // canvas.rs:50-52: the canvas's exporter is PngExporter (canvas.rs:23), whatever the path says
+  void save(const std::string& path) const {
+    const std::string png = to_png();
+    std::ofstream f(path, std::ios::binary);
+    if (!f || !f.write(png.data(), (std::streamsize)png.size()))
+      throw std::runtime_error("Canvas::save: cannot write `" + path + "`");
   }
 
  private:
@@ -777,6 +792,33 @@ class Camera {
     }
     size_t len = 0;
     check(rt_render_ppm(world.scene(), &desc_, max_depth, aa_samples, buf, bound, &len, stats), "rt_render_ppm");
+    take((const char*)buf, len);
+  }
+  // self.render(world).save(..)'s bytes (camera.rs:133-148, canvas.rs:50-52, image/png.rs:13-31),
+  // encoded on the device; aa_samples > 1 renders as render_multithreaded does.
+  std::string render_png(const World& world, unsigned max_depth = 5, unsigned aa_samples = 1,
+                         rt_stats* stats = nullptr) const {
+    std::string s;
+    render_png_with(world, max_depth, aa_samples, stats, [&](const char* p, size_t n) { s.assign(p, n); });
+    return s;
+  }
+  // The file in a pooled pinned block, handed to `take(p, n)` (as render_ppm_with).
+  template <typename F>
+  void render_png_with(const World& world, unsigned max_depth, unsigned aa_samples, rt_stats* stats, F&& take) const {
+    const size_t bound = rt_png_size(desc_.hsize, desc_.vsize);  // (0: not encodable; rt_render_png says why)
+    struct Block {
+      void* p;
+      ~Block() { rt_host_buffer_free(p); }
+    } blk{bound ? rt_host_buffer_alloc(bound) : nullptr};
+    std::string fallback;
+    char* buf = (char*)blk.p;
+    if (!buf) {
+      fallback.resize(std::max<size_t>(bound, 1));
+      buf = &fallback[0];
+    }
+    size_t len = 0;
+    check(rt_render_png(world.scene(), &desc_, max_depth, aa_samples, (uint8_t*)buf, bound, &len, stats),
+          "rt_render_png");
     take((const char*)buf, len);
   }
   RenderOpts render_opts;

@@ -17,6 +17,7 @@
 //     must be Integers and field-of-view a Real (lib.rs:403-425, 494-503).
 // Errors carry the reference's SceneParserError messages (error.rs:4-25).
 #pragma once
+#include <cctype>
 #include <fstream>
 #include <map>
 #include <memory>
@@ -82,16 +83,21 @@ class SceneParser {
     auto w = build_world();
     return scene_.camera->render(*w, max_depth, stats);
   }
-  // lib.rs:267-284 writes a PNG; this front-end writes the PPM (image/ppm.rs)
-  // (rendered and encoded on the device: rt_render_ppm; bytes = render(...).to_ppm())
+  // lib.rs:267-284 renders and saves through PngExporter: a path ending in `.png` (any
+  // letter case) gets that PNG (rendered and encoded on the device: rt_render_png; it
+  // decodes to render(...)'s quantised canvas); any other path gets the PPM
+  // (image/ppm.rs; rt_render_ppm; bytes = render(...).to_ppm())
   void render_to(const std::string& path, unsigned max_depth = 5) const {
     if (!scene_.camera) throw SceneParserError("missing required key `camera`");
     auto w = build_world();
-    const std::string ppm = scene_.camera->hsize() <= 12288 ? scene_.camera->render_ppm(*w, max_depth)
-                                                            : scene_.camera->render(*w, max_depth).to_ppm();
+    std::string ext = path.size() >= 4 ? path.substr(path.size() - 4) : std::string();
+    for (char& ch : ext) ch = (char)std::tolower((unsigned char)ch);
+    const std::string file = ext == ".png"                     ? scene_.camera->render_png(*w, max_depth)
+                             : scene_.camera->hsize() <= 12288 ? scene_.camera->render_ppm(*w, max_depth)
+                                                               : scene_.camera->render(*w, max_depth).to_ppm();
     std::ofstream f(path, std::ios::binary);
     if (!f) throw SceneParserError("cannot write `" + path + "`");
-    f.write(ppm.data(), (std::streamsize)ppm.size());
+    f.write(file.data(), (std::streamsize)file.size());
   }
 
   static bool is_add_element(const yaml::Node& el) {  // lib.rs:376-382

@@ -362,6 +362,8 @@ PYBIND11_MODULE(_rtamd, m) {
       .def("get_pixel", &Canvas::get_pixel)
       .def("set_pixel", &Canvas::set_pixel)
       .def("to_ppm", [](const Canvas& c) { return py::bytes(c.to_ppm()); })
+      .def("to_png", [](const Canvas& c) { return py::bytes(c.to_png()); })
+      .def("save", &Canvas::save, py::arg("path"))
       .def("to_numpy", [](const Canvas& c) {
         py::array_t<double> a({(py::ssize_t)c.height(), (py::ssize_t)c.width(), (py::ssize_t)3});
         std::memcpy(a.mutable_data(), c.data(), c.width() * c.height() * 3 * sizeof(double));
@@ -400,6 +402,38 @@ PYBIND11_MODULE(_rtamd, m) {
     }
     return len;
   }, py::arg("d_rgb"), py::arg("width"), py::arg("height"), py::arg("d_out"), py::arg("cap"), py::arg("stream") = 0);
+  // PngExporter::export (image/png.rs:13-31) of an (h, w, 3) array
+  m.def("canvas_to_png", [](py::array_t<double, py::array::c_style | py::array::forcecast> rgb) {
+    if (rgb.ndim() != 3 || rgb.shape(2) != 3) throw std::invalid_argument("expected (h, w, 3)");
+    const uint32_t h = (uint32_t)rgb.shape(0), w = (uint32_t)rgb.shape(1);
+    size_t len = 0;
+    check(rt_canvas_to_png(nullptr, w, h, nullptr, 0, &len), "rt_canvas_to_png");  // (refuses what a PNG cannot hold)
+    PyObject* obj = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)len);
+    if (!obj) throw py::error_already_set();
+    int rc;
+    {
+      py::gil_scoped_release nogil;
+      rc = rt_canvas_to_png(rgb.data(), w, h, (uint8_t*)PyBytes_AS_STRING(obj), len, &len);
+    }
+    if (rc != RT_OK) {
+      Py_DECREF(obj);
+      check(rc, "rt_canvas_to_png");
+    }
+    return py::reinterpret_steal<py::bytes>(obj);
+  });
+  // canvas_to_png of a device canvas into a device buffer (pointers as integers, e.g.
+  // torch tensors' data_ptr()); returns the file's length (d_out == 0: the length only)
+  m.def("canvas_to_png_device", [](uintptr_t d_rgb, uint32_t w, uint32_t h, uintptr_t d_out, size_t cap,
+                                   uintptr_t stream) {
+    size_t len = 0;
+    {
+      py::gil_scoped_release nogil;
+      check(rt_canvas_to_png_device((const double*)d_rgb, w, h, (uint8_t*)d_out, cap, &len, (void*)stream),
+            "rt_canvas_to_png_device");
+    }
+    return len;
+  }, py::arg("d_rgb"), py::arg("width"), py::arg("height"), py::arg("d_out"), py::arg("cap"), py::arg("stream") = 0);
+  m.def("png_size", &rt_png_size, py::arg("width"), py::arg("height"));
   m.def("quantize_u8", [](py::array_t<double, py::array::c_style | py::array::forcecast> v) {
     py::array_t<uint8_t> o(v.size());
     check(rt_quantize_u8(v.data(), (size_t)v.size(), o.mutable_data()), "rt_quantize_u8");
@@ -552,6 +586,41 @@ PYBIND11_MODULE(_rtamd, m) {
                              nullptr);
         }
         check(rc, "rt_render_ppm");
+        return len;
+      }, py::arg("world"), py::arg("out"), py::arg("max_depth") = 5, py::arg("aa_samples") = 1)
+      // camera.render(&world).save(..)'s bytes, rendered and encoded on the device (rt_render_png)
+      .def("render_png", [](const Camera& c, const World& w, unsigned max_depth, unsigned aa_samples, bool want_stats) {
+        rt_stats st{};
+        py::object out;
+        {
+          py::gil_scoped_release nogil;
+          c.render_png_with(w, max_depth, aa_samples, want_stats ? &st : nullptr, [&](const char* p, size_t n) {
+            char* dst = nullptr;
+            {
+              py::gil_scoped_acquire gil;
+              PyObject* b = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)n);
+              if (!b) throw py::error_already_set();
+              out = py::reinterpret_steal<py::object>(b);
+              dst = PyBytes_AS_STRING(b);
+            }
+            parallel_copy(dst, p, n);
+          });
+        }
+        return py::make_tuple(out, stats_dict(st));
+      }, py::arg("world"), py::arg("max_depth") = 5, py::arg("aa_samples") = 1, py::arg("want_stats") = false)
+      // the same into the caller's buffer (a frame loop's reused one): returns the file's length
+      .def("render_png_into", [](const Camera& c, const World& w, py::buffer out, unsigned max_depth,
+                                 unsigned aa_samples) {
+        py::buffer_info bi = out.request(true);
+        if (bi.ndim != 1 || bi.itemsize != 1) throw std::invalid_argument("expected a writable 1-D byte buffer");
+        size_t len = 0;
+        int rc;
+        {
+          py::gil_scoped_release nogil;
+          rc = rt_render_png(w.scene(), &c.desc(), max_depth, aa_samples, (uint8_t*)bi.ptr, (size_t)bi.size, &len,
+                             nullptr);
+        }
+        check(rc, "rt_render_png");
         return len;
       }, py::arg("world"), py::arg("out"), py::arg("max_depth") = 5, py::arg("aa_samples") = 1)
       .def_readwrite("render_opts", &Camera::render_opts, py::return_value_policy::reference_internal)

@@ -37,6 +37,7 @@
 #include "rt_kernels.hpp"
 #include "rt_layout.hpp"
 #include "rt_ppm_dev.hpp"
+#include "rt_png_dev.hpp"
 #include "rt_wavefront.hpp"
 
 using namespace rtamd;
@@ -139,6 +140,8 @@ struct rt_scene {
     size_t ppm_cap = 0;
     void* d_ppm_rows = nullptr;
     size_t ppm_rows_cap = 0;  // rows
+    uint8_t* d_png = nullptr;  // rt_render_png: the file, then the encoder's per-segment words
+    size_t png_cap = 0;
     void* h_stage[2] = {nullptr, nullptr};  // device-to-host copies into caller memory: two pinned chunks
     hipEvent_t stage_ev[2] = {nullptr, nullptr};
     // banded host renders (render_banded): a stream per band after the first, and the
@@ -213,6 +216,7 @@ struct rt_scene {
         (void)hipStreamDestroy(c.stream);
       }
       (void)hipFree(c.d_out); (void)hipFree(c.d_in); (void)hipFree(c.d_ppm); (void)hipFree(c.d_ppm_rows);
+      (void)hipFree(c.d_png);
       for (int k = 0; k < 2; ++k) {
         if (c.h_stage[k]) (void)hipHostFree(c.h_stage[k]);
         if (c.stage_ev[k]) (void)hipEventDestroy(c.stage_ev[k]);

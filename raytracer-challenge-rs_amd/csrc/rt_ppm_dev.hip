@@ -27,20 +27,13 @@
 #include <cstdint>
 
 #include "rt_ppm_dev.hpp"
+#include "rt_quant_dev.hpp"
 
 namespace rtamd {
 namespace {
 
 constexpr int kPpmBlock = 256;
 
-// scale_color_component (ppm.rs:73-75): round() is half away from zero like
-// f64::round; `as u8` saturates and maps NaN to 0.
-__device__ __forceinline__ unsigned q255(double v) {
-  const double s = round(v * 255.0);
-  if (!(s > 0.0)) return 0u;
-  if (s >= 255.0) return 255u;
-  return (unsigned)s;
-}
 __device__ __forceinline__ unsigned n_digits(unsigned q) { return q >= 100u ? 3u : q >= 10u ? 2u : 1u; }
 
 // The thread's contiguous range of pixels of a row of W.

@@ -1,7 +1,7 @@
 // rt_render.cpp — the render entry points of include/rt_render.h:
 // `Camera::render` (camera.rs:133-148) into device shards, frame batches and
 // block patterns, into a host canvas (row bands with overlapped copies), into
-// PPM text (image/ppm.rs:24-51), and the ray-batch entry points
+// PPM text (image/ppm.rs:24-51) or a PNG file (image/png.rs:13-31), and the ray-batch entry points
 // (`World::color_at`, `is_shadowed`, `intersect` + `prepare_computations`).
 #include "rt_api_internal.hpp"
 
@@ -494,6 +494,109 @@ int rt_canvas_to_ppm_device(const double* d_rgb, uint32_t width, uint32_t height
   if (e != hipSuccess) return fail(RT_ERR_HIP, std::string("rt_canvas_to_ppm_device: ") + hipGetErrorString(e));
   *out_len = hd.n + (size_t)body;
   if (d_out && cap < *out_len) return fail(RT_ERR_BUFFER_TOO_SMALL, "PPM buffer too small");
+  return RT_OK;
+  });
+}
+
+extern "C" int rtamd_png_check(uint32_t width, uint32_t height) noexcept;  // rt_png.cpp
+
+// bytes of a device buffer for the file and, behind it at a word boundary, the encoder's words
+static size_t png_buffer_bytes(uint64_t raw, size_t* part_at) {
+  *part_at = ((size_t)rtpng::file_len(raw) + 15) & ~(size_t)15;
+  return *part_at + png_part_words(raw) * sizeof(uint32_t);
+}
+
+int rt_render_png(const rt_scene* scene, const rt_camera_desc* camera, uint32_t max_depth, uint32_t aa_samples,
+                  uint8_t* out, size_t cap, size_t* out_len, rt_stats* stats) {
+  return guarded([&]() -> int {
+  if (!scene || !camera || !out_len) return fail(RT_ERR_INVALID_ARGUMENT, "null pointer");
+  if (!valid_aa(aa_samples)) return fail(RT_ERR_INVALID_ARGUMENT, "aa_samples must be 1, 2, 4, 8 or 16");
+  const uint32_t W = camera->hsize, H = camera->vsize;
+  if (const int bad = rtamd_png_check(W, H)) return bad;
+  const uint64_t n_pix = (uint64_t)W * H, raw = rtpng::raw_len(W, H);
+  if (n_pix * aa_samples >= (1ull << 31)) return fail(RT_ERR_INVALID_ARGUMENT, "canvas too large for one launch");
+  const size_t len = (size_t)rtpng::file_len(raw);  // known before anything is rendered
+  *out_len = len;
+  if (!out) return RT_OK;
+  if (cap < len) return fail(RT_ERR_BUFFER_TOO_SMALL, "PNG buffer too small");
+  rt_scene* s = const_cast<rt_scene*>(scene);
+  std::unique_lock<std::mutex> lk(s->mu);
+  auto t0 = std::chrono::steady_clock::now();
+  RT_DEVICE(s->device);
+  CtxLease cx{s, lk};
+  RT_TAKE_CTX(cx);
+  rt_scene::HostCtx* c = cx.c;
+  int rc = ensure_dev_buffer(&c->d_out, &c->out_cap, n_pix * 3);
+  if (rc != RT_OK) return rc;
+  size_t part_at = 0;
+  const size_t need = png_buffer_bytes(raw, &part_at);
+  if (c->png_cap < need) {
+    if (c->d_png) (void)hipFree(c->d_png);
+    c->d_png = nullptr;
+    c->png_cap = 0;
+    RT_HIP(hipMalloc((void**)&c->d_png, need));
+    c->png_cap = need;
+  }
+  struct Drain {  // no kernel or copy of this call outlives it (the context goes back to the pool)
+    hipStream_t st;
+    ~Drain() {
+      if (hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
+    }
+  } drain{c->stream};
+  const WfJob job = WfJob::camera_shard(to_dev_camera(*camera), (uint32_t)(n_pix * aa_samples), aa_samples, max_depth,
+                                        c->d_out, H);
+  // As rt_render_ppm: the render and the encoder in one pass of the stream, one wait, then the
+  // workspace's overflow record; a frame that outgrew its arenas is rendered and encoded again.
+  PinGuard pin(s, &lk);
+  RenderCall call(&lk);
+  call.stats = call.time = stats != nullptr;
+  if (!stats) call.keep_pin = &pin;
+  RenderResult r;
+  if ((rc = run_render(s, job, c->stream, call, &r)) != RT_OK) return rc;
+  auto encode = [&]() -> int {
+    RT_HIP(png_encode_device(c->d_out, W, H, c->d_png, (uint32_t*)(c->d_png + part_at), c->stream));
+    lk.unlock();
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    lk.lock();
+    if (e != hipSuccess) return fail(RT_ERR_HIP, std::string("rt_render_png: ") + hipGetErrorString(e));
+    return RT_OK;
+  };
+  if ((rc = encode()) != RT_OK) return rc;
+  bool over = false;
+  if ((rc = settle(pin, s->sizing, &over)) != RT_OK) return rc;
+  if (over) {  // (the canvas was poisoned: render it again, growing the arenas until it fits)
+    RenderCall again(&lk);
+    again.sync = true;
+    if ((rc = run_render(s, job, c->stream, again)) != RT_OK) return rc;
+    if ((rc = encode()) != RT_OK) return rc;
+  }
+  const int d2h = s->tune.d2h;
+  lk.unlock();
+  if ((rc = copy_to_host(c, d2h, out, c->d_png, len, c->stream)) != RT_OK) return rc;
+  if (stats)
+    fill_stats(stats, r.stats, r.ms,
+               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  return RT_OK;
+  });
+}
+
+int rt_canvas_to_png_device(const double* d_rgb, uint32_t width, uint32_t height, uint8_t* d_out, size_t cap,
+                            size_t* out_len, void* stream) {
+  return guarded([&]() -> int {
+  if (!out_len) return fail(RT_ERR_INVALID_ARGUMENT, "null pointer");
+  if (const int bad = rtamd_png_check(width, height)) return bad;
+  const uint64_t raw = rtpng::raw_len(width, height);
+  *out_len = (size_t)rtpng::file_len(raw);
+  if (!d_out) return RT_OK;  // the length alone: it follows from the size
+  if (!d_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "null pointer");
+  if (cap < *out_len) return fail(RT_ERR_BUFFER_TOO_SMALL, "PNG buffer too small");
+  hipStream_t st = (hipStream_t)stream;
+  void* part = nullptr;
+  RT_HIP(hipMallocAsync(&part, png_part_words(raw) * sizeof(uint32_t), st));
+  hipError_t e = png_encode_device(d_rgb, width, height, d_out, (uint32_t*)part, st);
+  (void)hipFreeAsync(part, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return fail(RT_ERR_HIP, std::string("rt_canvas_to_png_device: ") + hipGetErrorString(e));
   return RT_OK;
   });
 }
