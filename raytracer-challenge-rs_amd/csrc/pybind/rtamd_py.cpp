@@ -86,7 +86,7 @@ extern "C" int rtamd_nccl_gather_f64(const double* send, double* recv, size_t co
 extern "C" int rtamd_nccl_comm_destroy(void* comm);
 extern "C" int rtamd_wf_profile(const rt_scene* s, int enable, double out[40]);
 extern "C" int rtamd_wf_gen_counts(const rt_scene* s, unsigned* out, int max);
-extern "C" int rtamd_wf_plan(const rt_scene* s, long long out[12]);
+extern "C" int rtamd_wf_plan(const rt_scene* s, long long out[14]);
 extern "C" int rtamd_scene_tuning_set(const rt_scene* s, const char* key, int value);
 extern "C" int rtamd_render_shard_host(const rt_scene* scene, const rt_camera_desc* camera, uint32_t max_depth,
                                        uint32_t aa_samples, uint32_t row_block, uint32_t shard, uint32_t n_shards,
@@ -801,7 +801,7 @@ PYBIND11_MODULE(_rtamd, m) {
   // the image plans of the last render's fused launches (rt_wf_plan.hpp): generation 0's and the
   // last deeper generation's; lane -1 = none. lds_spheres / lds_deltas: the kLdsSpheres / kLdsDeltas flags
   m.def("_wf_plan", [](const World& w) {
-    long long o[12] = {0};
+    long long o[14] = {0};
     check(rtamd_wf_plan(w.scene(), o), "wf_plan");
     py::dict d;
     const char* which[2] = {"primary", "secondary"};
@@ -818,6 +818,8 @@ PYBIND11_MODULE(_rtamd, m) {
     py::dict t;  // the triangle hierarchy (tri_trace): `ran` = the last render walked it
     t["records"] = o[8]; t["depth"] = o[9]; t["nodes"] = o[10]; t["ran"] = o[11] != 0;
     d["triangles"] = t;
+    d["n_tris"] = o[12];  // what launch_fused chooses the TRIS and CSG kernels by
+    d["n_csg_units"] = o[13];
     return d;
   }, py::arg("world"));
   m.def("_tuning_set", [](const std::string& k, int v) { check(rtamd_tuning_set(k.c_str(), v), "tuning"); });

@@ -3,11 +3,13 @@
 (the C oracle under oracle/ has no Csg).
 
 Input: the bytes the library itself consumes (World.descs_bytes, nodes_bytes,
-shape_nodes, shape_sides, lights_bytes; for a world without a Csg groups_bytes
-and shape_groups). Output as tests/mesh_ref.py: per ray the 24 doubles of
-rt_hit_batch, per frame the canvas and the reference's counters. Kinds 0-4
-(sphere, plane, cube, cylinder, cone), groups and Csg nodes; patterns and
-triangles are refused.
+shape_nodes, shape_sides, lights_bytes, triangles_bytes; for a world without a
+Csg groups_bytes and shape_groups). Output as tests/mesh_ref.py: per ray the 24
+doubles of rt_hit_batch, per frame the canvas and the reference's counters.
+Every world the library accepts: kinds 0-4 (sphere, plane, cube, cylinder,
+cone), Triangle and SmoothTriangle (kinds 5 and 6) at the top level or under
+groups, groups, Csg nodes and the five patterns (mesh_ref's `lighting`). A
+triangle under a Csg is refused, as the library refuses it.
 
 How it computes (the rules of mesh_ref.py): IEEE binary64 scalars, never fused,
 no dot / matmul / sum. Every ray builds the reference's lists as the reference
@@ -16,20 +18,25 @@ matrix after another down a Csg chain, never a product), Group::intersect and
 Csg::local_intersect gate on their boxes, a Csg sorts left ++ right stably and
 runs filter_intersections as written (csg.rs:71-91), `includes` is membership
 in the left subtree, World::intersect sorts everything again; then the full
-`containers` walk (mesh_ref.MeshRef.prepare).
+`containers` walk (mesh_ref.MeshRef.prepare). A triangle's Shape::intersect is
+ray_transform by its own inverse, then mesh_ref.triangle_solve; all triangles
+of a world are solved in one element-wise numpy call per world ray (no group
+changes the ray, and no triangle lies under a Csg), and each one's answer is
+taken, and counted, where the tree walk reaches it.
 
 `csg_ties`: the number of adjacent equal-t pairs met in any Csg node's sorted
 list since the object was made (the reference's sort is unstable there).
 """
 import numpy as np
 
-from mesh_ref import CAMERA, COUNTERS, EPSILON, GROUP, INF, SHAPE, MeshRef, mat_point, normalize, sub  # noqa: F401
+from mesh_ref import (CAMERA, COUNTERS, EPSILON, GROUP, INF, SHAPE, TRI, MeshRef, mat_point, mat_vector,  # noqa: F401
+                      normalize, sub, triangle_solve)
 
 NODE = np.dtype([("kind", "<i4"), ("parent", "<i4"), ("side", "<i4"), ("operation", "<i4"), ("min", "<f8", 3),
                  ("max", "<f8", 3), ("inverse", "<f8", 16)])
 assert NODE.itemsize == 192
 
-SPHERE, PLANE, CUBE, CYLINDER, CONE = 0, 1, 2, 3, 4
+SPHERE, PLANE, CUBE, CYLINDER, CONE, TRIANGLE, SMOOTH = 0, 1, 2, 3, 4, 5, 6
 NODE_GROUP, NODE_CSG = 0, 1
 UNION, INTERSECTION, DIFFERENCE = 0, 1, 2
 F = np.float64
@@ -160,7 +167,7 @@ def local_intersect(kind, mn, mx, closed, o, d):
 
 class CsgRef(MeshRef):
     def __init__(self, descs_bytes, nodes_bytes=b"", shape_nodes=None, shape_sides=None, lights_bytes=b"",
-                 groups_bytes=b"", shape_groups=None):
+                 groups_bytes=b"", shape_groups=None, triangles_bytes=b""):
         self.s = np.frombuffer(descs_bytes, dtype=SHAPE)
         n = len(self.s)
         nodes = np.frombuffer(nodes_bytes, dtype=NODE)
@@ -173,9 +180,26 @@ class CsgRef(MeshRef):
         self.shape_node = list(shape_nodes) if shape_nodes is not None and len(nodes) else [-1] * n
         self.shape_side = list(shape_sides) if shape_sides is not None and len(shape_sides) else [0] * n
         self.lights = np.frombuffer(lights_bytes, dtype=np.float64).reshape(-1, 6)
-        if not np.isin(self.s["kind"], (SPHERE, PLANE, CUBE, CYLINDER, CONE)).all() or \
-                (self.s["pattern_kind"] != -1).any():
-            raise ValueError("csg_ref: kinds 0-4 and unpatterned materials only")
+        if not np.isin(self.s["kind"], (SPHERE, PLANE, CUBE, CYLINDER, CONE, TRIANGLE, SMOOTH)).all():
+            raise ValueError("csg_ref: kinds 0-6 only")
+        # the triangles, as MeshRef holds them: columns, for one element-wise solve per world ray
+        self.tris = np.frombuffer(triangles_bytes, dtype=TRI)
+        tri_idx = np.flatnonzero(self.s["kind"] >= TRIANGLE)
+        if len(tri_idx) != len(self.tris):
+            raise ValueError("csg_ref: triangles_bytes does not match the shapes")
+        self.tri_of = {int(i): j for j, i in enumerate(tri_idx)}
+        for i in tri_idx:
+            g = self.shape_node[int(i)]
+            while g >= 0:
+                if int(nodes["kind"][g]) == NODE_CSG:
+                    raise ValueError("csg_ref: a triangle under a Csg (the library refuses it)")
+                g = int(nodes["parent"][g])
+        self.tri_inv = [self.s["inverse"][tri_idx, e].copy() for e in range(12)]
+        col = lambda a: (a[:, 0].copy(), a[:, 1].copy(), a[:, 2].copy())
+        self.tp1 = col(self.tris["p1"])
+        self.te1 = sub(col(self.tris["p2"]), self.tp1)  # Triangle::new: e1 = p2 - p1, e2 = p3 - p1
+        self.te2 = sub(col(self.tris["p3"]), self.tp1)
+        self._solved = None
         self.counts = dict.fromkeys(COUNTERS, 0)
         self.csg_ties = 0
         # the tree: each node's children in the reference's order (the shapes come depth first)
@@ -203,19 +227,26 @@ class CsgRef(MeshRef):
     @classmethod
     def from_world(cls, w):
         return cls(w.descs_bytes(), w.nodes_bytes(), w.shape_nodes(), w.shape_sides(), w.lights_bytes(),
-                   w.groups_bytes(), w.shape_groups())
+                   w.groups_bytes(), w.shape_groups(), w.triangles_bytes())
 
-    # ---- Shape::intersect (geometry/mod.rs:46-49) of a primitive: [(t, object)]
+    # ---- Shape::intersect (geometry/mod.rs:46-49) of a primitive: [(t, object, u, v)]
     def _shape(self, i, o, d):
         s = self.s[i]
         kind = int(s["kind"])
+        if kind >= TRIANGLE:  # triangle.rs:63-90, smooth_triangle.rs:74-101: solved with all the others
+            ok, t, u, v = self._solved
+            j = self.tri_of[i]
+            self.counts["other_tests"] += 1
+            if not ok[j]:
+                return []
+            return [(t[j], i, float(u[j]), float(v[j]))] if kind == SMOOTH else [(t[j], i, None, None)]
         lo, ld = ray_transform(s["inverse"], o, d)
         ts, disc = local_intersect(kind, s["minimum"], s["maximum"], bool(s["closed"]), lo, ld)
         c = self.counts
         c["sphere_tests" if kind == SPHERE else "plane_tests" if kind == PLANE else "other_tests"] += 1
         if disc:
             c["sphere_disc_ge0"] += 1
-        return [(t, i) for t in ts]
+        return [(t, i, None, None) for t in ts]
 
     def _child(self, c, o, d):
         return self._shape(c[3], o, d) if c[2] == "shape" else self._node(c[3], o, d)
@@ -251,15 +282,20 @@ class CsgRef(MeshRef):
         d = tuple(F(x) for x in d)
         xs = []
         with np.errstate(all="ignore"):
+            if len(self.tris):  # Ray::transform by each triangle's own inverse, then local_intersect
+                self._solved = triangle_solve(self.tp1, self.te1, self.te2, mat_point(self.tri_inv, o),
+                                              mat_vector(self.tri_inv, d))
             for c in self.kids[-1]:
                 xs.extend(self._child(c, o, d))
         if any(x[0] != x[0] for x in xs):
             raise ValueError("csg_ref: a NaN t (the reference's sort panics)")
         xs.sort(key=lambda x: x[0])
-        return [(float(x[0]), x[1], None, None) for x in xs]
+        return [(float(x[0]), x[1], x[2], x[3]) for x in xs]
 
     def normal_at(self, i, point, hit):  # geometry/mod.rs:51-56: the leaf's own matrices on the world point
         s = self.s[i]
+        if int(s["kind"]) >= TRIANGLE:
+            return MeshRef.normal_at(self, i, point, hit)
         inv = [float(x) for x in s["inverse"]]
         p = (inv[0] * point[0] + inv[1] * point[1] + inv[2] * point[2] + inv[3],
              inv[4] * point[0] + inv[5] * point[1] + inv[6] * point[2] + inv[7],

@@ -5,7 +5,8 @@ Input: the bytes the library itself consumes (World.descs_bytes, groups_bytes,
 shape_groups, triangles_bytes, lights_bytes; Camera.desc_bytes). Output: per
 ray the 24 doubles of rt_hit_batch; per frame the canvas and the reference's
 rays_* / *_tests counts. Spheres, planes, Triangle, SmoothTriangle, group
-gates and unpatterned materials; anything else is refused.
+gates and the five patterns (Pattern::color_at_shape in `lighting`); any other
+kind of shape is refused.
 
 How it computes: Python floats, or element-wise numpy over the shapes of one
 kind (both IEEE binary64, never fused); no dot / matmul / einsum / sum;
@@ -16,7 +17,8 @@ of prepare_computations literally (intersection.rs:63-90); none of the
 library's shortcuts (top-2 containers, culling, skipped shadow rays).
 
 Pinned at both ends by tests/test_mesh_ref.py: bit for bit against liboracle
-on triangle-free scenes, and the reference's triangle KATs.
+on triangle-free scenes (patterned ones included), and the reference's
+triangle and pattern KATs.
 """
 import math
 
@@ -141,6 +143,55 @@ def schlick(eyev, normalv, n1, n2):  # intersection.rs:147-162
     return r0 + (1.0 - r0) * (x * ((x * x) * (x * x)))  # powi(5): x * (x^2)^2
 
 
+# ---- pattern/{test_pattern,stripe,gradient,ring,checkers}.rs; `%` on an f64 is fmod
+PATTERN_NONE, PATTERN_TEST, PATTERN_STRIPE, PATTERN_GRADIENT, PATTERN_RING, PATTERN_CHECKERS = -1, 0, 1, 2, 3, 4
+
+
+def floor(x):  # f64::floor (math.floor makes an int and refuses inf and NaN)
+    return float(np.floor(x))
+
+
+def fmod(x, y):  # `%` on an f64 (math.fmod raises where C's fmod gives a NaN: an infinite x)
+    try:
+        return math.fmod(x, y)
+    except ValueError:
+        return float("nan")
+
+
+def as_isize(x):  # `f64 as isize`: saturating, a NaN goes to 0
+    if x != x:
+        return 0
+    if x >= 9223372036854775807.0:
+        return 9223372036854775807
+    if x <= -9223372036854775808.0:
+        return -9223372036854775808
+    return int(x)
+
+
+def pattern_color_at(kind, a, b, p):
+    """<Kind>Pattern::color_at on floats: `a`, `b` the pattern's colours, `p` the pattern point."""
+    if kind == PATTERN_TEST:  # test_pattern.rs:7-9
+        return (p[0], p[1], p[2])
+    if kind == PATTERN_STRIPE:  # stripe.rs:14-20
+        return a if fmod(floor(p[0]), 2.0) == 0.0 else b
+    if kind == PATTERN_GRADIENT:  # gradient.rs:14-18: a + (b - a) * fraction
+        fraction = p[0] - floor(p[0])
+        return add(a, scale(sub(b, a), fraction))
+    if kind == PATTERN_RING:  # ring.rs:14-21
+        distance = floor(math.sqrt(p[0] * p[0] + p[2] * p[2]))
+        return a if fmod(distance, 2.0) == 0.0 else b
+    if kind == PATTERN_CHECKERS:  # checkers.rs:14-21: an integer `%`; its sign rule does not matter to `== 0`
+        distance = floor(p[0]) + floor(p[1]) + floor(p[2])
+        return a if as_isize(distance) % 2 == 0 else b
+    raise ValueError("mesh_ref: bad pattern kind")
+
+
+def pattern_color_at_shape(kind, a, b, pattern_inverse, shape_inverse, world_point):  # pattern/mod.rs:39-49
+    object_point = mat_point(shape_inverse, world_point)
+    pattern_point = mat_point(pattern_inverse, object_point)
+    return pattern_color_at(kind, a, b, pattern_point)
+
+
 class MeshRef:
     def __init__(self, descs_bytes, groups_bytes=b"", shape_groups=None, triangles_bytes=b"", lights_bytes=b""):
         self.s = np.frombuffer(descs_bytes, dtype=SHAPE)
@@ -151,8 +202,8 @@ class MeshRef:
         tris = np.frombuffer(triangles_bytes, dtype=TRI)
         self.lights = np.frombuffer(lights_bytes, dtype=np.float64).reshape(-1, 6)
         kind = self.s["kind"]
-        if not np.isin(kind, (SPHERE, PLANE, TRIANGLE, SMOOTH)).all() or (self.s["pattern_kind"] != -1).any():
-            raise ValueError("mesh_ref: spheres, planes, triangles and unpatterned materials only")
+        if not np.isin(kind, (SPHERE, PLANE, TRIANGLE, SMOOTH)).all():
+            raise ValueError("mesh_ref: spheres, planes and triangles only")
         self.idx = {k: np.flatnonzero(kind == k) for k in (SPHERE, PLANE)}
         self.idx["tri"] = np.flatnonzero(kind >= TRIANGLE)
         if len(self.idx["tri"]) != len(tris):
@@ -330,7 +381,13 @@ class MeshRef:
 
     def lighting(self, i, L, point, eyev, normalv, in_shadow):  # material.rs:38-82
         s = self.s[i]
-        color = tuple(float(x) for x in s["color"])
+        if int(s["pattern_kind"]) != PATTERN_NONE:  # material.rs:47-51
+            color = pattern_color_at_shape(int(s["pattern_kind"]), tuple(float(x) for x in s["pattern_a"]),
+                                           tuple(float(x) for x in s["pattern_b"]),
+                                           [float(x) for x in s["pattern_inverse"]], [float(x) for x in s["inverse"]],
+                                           point)
+        else:
+            color = tuple(float(x) for x in s["color"])
         intensity = tuple(float(x) for x in L[3:])
         effective = (color[0] * intensity[0], color[1] * intensity[1], color[2] * intensity[2])
         lightv = normalize(sub(tuple(float(x) for x in L[:3]), point))
@@ -346,7 +403,10 @@ class MeshRef:
             if reflect_dot_eye <= 0.0:
                 specular = (0.0, 0.0, 0.0)
             else:
-                factor = math.pow(reflect_dot_eye, float(s["shininess"]))
+                try:
+                    factor = math.pow(reflect_dot_eye, float(s["shininess"]))
+                except OverflowError:  # f64::powf gives inf (an unnormalised eye vector)
+                    factor = INF
                 specular = scale(scale(intensity, float(s["specular"])), factor)
         return add(add(ambient, diffuse), specular)
 

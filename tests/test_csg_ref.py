@@ -6,6 +6,13 @@ glass, a divided group, a shadowless shape, two lights) its hit records, a
 24x16 frame and the counters equal liboracle's bit for bit; the oracle is
 itself pinned by the reference's KATs.
 Pin 2: the reference's Csg KATs (csg.rs:142-303) through the checker's functions.
+Pin 3: on worlds with triangles (test_gpu_mesh.py's divided torus, flat and
+smooth, and its 8 loose triangles) it equals the mesh checker (tests/mesh_ref.py,
+itself pinned by tests/test_mesh_ref.py) bit for bit over all 24 outputs of the
+hit records, a 24x16 frame and the counters.
+Pin 4: on four rtamd.scenes.fuzz seeds that together hold all five pattern
+kinds, each with and without a pattern transform (asserted from descs_bytes),
+its 24x16 frame and counters equal liboracle's bit for bit.
 """
 import math
 import random
@@ -14,6 +21,7 @@ import numpy as np
 import pytest
 
 import csg_ref
+import mesh_ref
 
 
 def _world(rt, seed):
@@ -166,3 +174,84 @@ def test_a_csg_shape_has_a_bounding_box_that_contains_its_children(rt):  # csg.r
     node = np.frombuffer(w.nodes_bytes(), dtype=csg_ref.NODE)[0]
     assert list(node["min"]) == [-1, -1, -1] and list(node["max"]) == [3, 4, 5]
     assert node["kind"] == csg_ref.NODE_CSG and node["operation"] == csg_ref.DIFFERENCE and node["parent"] == -1
+
+
+# ---------------------------------------------------------------- triangles: the mesh checker's worlds
+def _mesh_world(rt, name):
+    from rtamd import scenes
+    if name == "loose8":
+        from test_gpu_mesh import _loose8
+        w, cam = _loose8(rt)
+        return w, cam, [-2.5, 0.2, -1.5], [2.5, 3.0, 2.5]
+    _, w, cam, _ = scenes.mesh_scene(24, 16, 10, 10, name == "smooth", 4, depth=3)
+    g = np.frombuffer(w.groups_bytes(), dtype=mesh_ref.GROUP)[0]  # the torus group's box
+    return w, cam, g["min"], g["max"]
+
+
+@pytest.mark.parametrize("name", ["flat", "smooth", "loose8"])
+def test_checker_equals_the_mesh_checker_on_triangle_worlds(rt, name):
+    from test_gpu_mesh import _rays
+    w, cam, lo, hi = _mesh_world(rt, name)
+    kinds = np.frombuffer(w.descs_bytes(), dtype=csg_ref.SHAPE)["kind"]
+    assert (kinds >= 5).sum() == (8 if name == "loose8" else 201) and w.nodes_bytes() == b""
+    ref, mref = csg_ref.CsgRef.from_world(w), mesh_ref.MeshRef.from_world(w)
+    rays = _rays(3, 400, lo, hi)
+    got, want = ref.hit_batch(rays), mref.hit_batch(rays)
+    assert got.tobytes() == want.tobytes()
+    hit = want[want[:, 0] >= 0]
+    assert (kinds[hit[:, 0].astype(int)] >= 5).sum() > 20 and len(set(hit[:, 21])) > 1
+    assert ref.counts == mref.counts and ref.counts["other_tests"] > 0
+    img, st = ref.render(cam.desc_bytes(), 3)
+    mimg, mst = mref.render(cam.desc_bytes(), 3)
+    assert img.tobytes() == mimg.tobytes(), np.abs(img - mimg).max()
+    assert st == mst and st["other_tests"] > 0 and st["rays_reflect"] > 0 and st["rays_refract"] > 0
+    assert ref.csg_ties == 0
+
+
+def test_checker_refuses_a_triangle_under_a_csg(rt):
+    """As the library does (test_gpu_csg.py::test_beyond_the_caps_is_refused); the records are made by
+    hand, since the library does not flatten such a world."""
+    w = rt.World()
+    w.add_object(rt.Csg(rt.Operation.Union, rt.Sphere(), rt.Cube()))
+    descs = np.frombuffer(w.descs_bytes(), dtype=csg_ref.SHAPE).copy()
+    descs["kind"][1] = csg_ref.TRIANGLE
+    tri = np.zeros(1, dtype=csg_ref.TRI)
+    tri["p1"], tri["p2"], tri["p3"] = (0, 1, 0), (-1, 0, 0), (1, 0, 0)
+    with pytest.raises(ValueError, match="under a Csg"):
+        csg_ref.CsgRef(descs.tobytes(), w.nodes_bytes(), w.shape_nodes(), w.shape_sides(), w.lights_bytes(),
+                       triangles_bytes=tri.tobytes())
+    with pytest.raises(ValueError, match="does not match"):
+        csg_ref.CsgRef(descs.tobytes(), w.nodes_bytes(), w.shape_nodes(), w.shape_sides(), w.lights_bytes())
+
+
+# ---------------------------------------------------------------- patterns: the fuzz scenes
+PATTERN_SEEDS = (0, 59, 17, 5)  # 0 and 59 are among test_gpu_variants.FUZZ_SEEDS
+
+
+def _pattern_cover(w):
+    """{(pattern kind, has a pattern transform)} of a world, from its shape records."""
+    d = np.frombuffer(w.descs_bytes(), dtype=csg_ref.SHAPE)
+    ident = np.eye(4).ravel()
+    return {(int(k), bool((t != ident).any())) for k, t in zip(d["pattern_kind"], d["pattern_transform"]) if k >= 0}
+
+
+def test_pattern_seeds_hold_every_kind_with_and_without_a_transform(rt):
+    from rtamd import scenes
+    import test_gpu_variants
+    cover = set()
+    for seed in PATTERN_SEEDS:
+        cover |= _pattern_cover(scenes.fuzz(seed, 24, 16)[0])
+    assert cover == {(k, t) for k in range(5) for t in (False, True)}
+    assert len(PATTERN_SEEDS) == 4 and set(PATTERN_SEEDS) & set(test_gpu_variants.FUZZ_SEEDS)
+
+
+@pytest.mark.parametrize("seed", PATTERN_SEEDS)
+def test_checker_patterned_frame_and_counters_equal_the_oracle_bitwise(rt, oracle, seed):
+    from rtamd import scenes
+    w, cam, depth = scenes.fuzz(seed, 24, 16)
+    assert _pattern_cover(w)
+    ref = csg_ref.CsgRef.from_world(w)
+    img, st = ref.render(cam.desc_bytes(), depth)
+    oimg, ost = oracle.OracleWorld.from_world(w).render(cam.desc_bytes(), depth)
+    assert img.tobytes() == oimg.tobytes(), np.abs(img - oimg).max()
+    assert st == {k: ost[k] for k in st}

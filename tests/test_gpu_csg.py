@@ -321,11 +321,15 @@ def test_scene_b_runs_the_lds_stack_image(rendered):
 
 def test_lens_before_a_patterned_wall(rt):
     w, cam, depth = _scene_e(rt)
-    with pytest.raises(ValueError):
-        csg_ref.CsgRef.from_world(w)  # the checker refuses patterns: exhaustive = fast
-    fast, _ = cam.render(w, depth, False)
+    ref = csg_ref.CsgRef.from_world(w)  # (the checker has the patterns: mesh_ref's `lighting`)
+    img, rst = ref.render(cam.desc_bytes(), depth)
+    assert ref.csg_ties == 0
+    fast, fst = cam.render(w, depth, True, False)
     exh, est = cam.render(w, depth, True, True)
+    assert exh.to_numpy().tobytes() == img.tobytes(), np.abs(exh.to_numpy() - img).max()
     assert fast.to_numpy().tobytes() == exh.to_numpy().tobytes()
+    for k in COUNTS:
+        assert fst[k] == rst[k] and est[k] == rst[k], (k, fst[k], est[k], rst[k])
     assert est["rays_refract"] > 50 and len(np.unique(exh.to_numpy().reshape(-1, 3), axis=0)) > 20
 
 
@@ -505,25 +509,22 @@ def test_at_the_caps_renders_and_matches(rt):
     w.add_object(g)
     _lights(rt, w)
     cam = _camera(rt, (0, 1.0, -5.0), (0, 0, 0))
-    fast, _ = cam.render(w, 3, False)
+    fast, fst = cam.render(w, 3, True, False)
     exh, est = cam.render(w, 3, True, True)
     assert fast.to_numpy().tobytes() == exh.to_numpy().tobytes()
-    w2 = rt.World()  # the same world without the triangle, for the checker (it has no triangles)
-    w2.add_object(floor)
-    w2.add_object(_union_of(rt, MAX_LEAVES))
-    _lights(rt, w2)
-    ref = csg_ref.CsgRef.from_world(w2)
+    ref = csg_ref.CsgRef.from_world(w)  # the whole world, the triangle included
     rays = np.array([cam_ray for cam_ray in _pixel_rays(ref, cam)])
-    got = w2.hit_batch(rays)
+    got = w.hit_batch(rays)
     want = ref.hit_batch(rays)
     assert ref.csg_ties == 0
     assert np.array_equal(got[:, 0], want[:, 0]) and got[:, 1:23].tobytes() == want[:, 1:23].tobytes()
     assert (want[:, 0] > 0).sum() > 30
+    tri = int(np.flatnonzero(ref.s["kind"] == csg_ref.TRIANGLE)[0])
+    assert (want[:, 0] == tri).sum() >= 3  # the triangle is in the frame
     img, rst = ref.render(cam.desc_bytes(), 3)
-    one, st = cam.render(w2, 3, True, True)
-    assert one.to_numpy().tobytes() == img.tobytes()
+    assert exh.to_numpy().tobytes() == img.tobytes()
     for k in COUNTS:
-        assert st[k] == rst[k], k
+        assert est[k] == rst[k] and fst[k] == rst[k], k
 
 
 def _pixel_rays(ref, cam):

@@ -1,14 +1,24 @@
 """Every fast-path kernel variant and every outcome of the LDS plan, on the GPU.
 
 Per generation the fast path launches one instantiation of
-wf_trace_fused<PRIMARY, QUADS, LANE, TALLY, CAM> (launch_fused_q in
-rt_wavefront.hip, launch_glb_lane in rt_wavefront_glb.hip): 4 for LANE 0 (the
-wave traversal: QUADS x TALLY, always camera rays) and 8 for each of LANE 15,
-14, 4, 3 and 1 (QUADS x TALLY x CAM), 44 in all. wf_plan_image
+wf_trace_fused<PRIMARY, QUADS, LANE, TALLY, CAM, TRIS, CSG> (launch_fused_q in
+rt_wavefront.hip, launch_glb_lane in rt_wavefront_glb.hip), 88 in all, in three
+classes that launch_fused chooses from the scene:
+  TRIS = CSG = false (no triangle, no Csg): 4 for LANE 0 (the wave traversal:
+    QUADS x TALLY, always camera rays) and 8 for each of LANE 15, 14, 4, 3 and
+    1 (QUADS x TALLY x CAM), 44;
+  TRIS (triangles, no Csg): the QUADS kernels with the triangle loop and walk,
+    2 for LANE 0 and 4 for each other LANE (TALLY x CAM), 22;
+  TRIS, CSG (a Csg node anywhere): the triangle kernels with the Csg units'
+    loop, 22 again.
+LANE 4, 3 and 1 live in rt_wavefront_glb.o, built with other compiler flags
+than the rest. wf_plan_image
 (rt_wf_plan.hpp) chooses the LANE and what the block stages in LDS: the
 kLdsSpheres / kLdsDeltas flags and a treelet of n_top nodes. `_wf_plan(world)`
 reads back the plan that ran, so every case below asserts the lane, the flags
-and n_top it was written for and fails if it did not reach them.
+and n_top it was written for and fails if it did not reach them; its n_tris and
+n_csg_units are what launch_fused chooses the class by, held to the world's own
+records (_tris_csg).
 
 Part 1 (test_variants_*): scenes x knob settings x modes. The scenes: six
 rtamd.scenes.fuzz seeds (diagonal ellipsoids, general-transform spheres, cubes,
@@ -26,9 +36,23 @@ the exhaustive GPU result of the same call, counters included; once per scene
 the exhaustive frame is bitwise the CPU oracle's, with equal counters and PPM
 bytes. No tolerance anywhere.
 
+The TRIS and CSG classes run the same variants and modes over five scenes built
+here (24x16, depth 3, two lights, 400 batch rays): `mesh` (two diagonal glass
+spheres, a divided smooth 72-triangle torus, a loose shadowless triangle, a
+cube, a patterned triangle group), `mesh_nodiag` (a floor, a flat torus and a
+cone: the triangle hierarchy alone opens the fused generations, so generation 0
+runs LANE 3 and 1 with CAM = true), `csg` (test_gpu_csg.py's scene (a) with a
+checkers pattern on one leaf of the die), `csg_nodiag` (its scene (b): a
+transformed Csg, a Csg in a divided group, grouped spheres only) and `mixed` (a
+die, a divided 32-triangle mesh in one group with a second Csg, two diagonal
+spheres, a patterned floor, a closed cylinder). The oracle refuses these
+worlds; their yardstick is the checker of tests/csg_ref.py (pinned by
+tests/test_csg_ref.py): once per scene the exhaustive GPU frame and counters
+equal the checker's bit for bit, with csg_ties == 0.
+
 test_every_reachable_kernel_variant_ran shows from the asserted readouts that
-the sweep launched every (LANE, QUADS, TALLY, CAM) tuple of LAUNCH_TABLE that
-the public calls can reach.
+the sweep launched every (LANE, QUADS, TALLY, CAM, TRIS, CSG) tuple of
+LAUNCH_TABLE that the public calls can reach, class by class.
 
 Part 2 (test_size_*): the plan outcomes that need size, on 64x36 to 64x64
 frames. Measured on an MI355X (SIZE_TABLE, asserted by the tests): the plan of
@@ -80,18 +104,23 @@ def _static_lds(lane):  # rt_wf_plan.hpp lane_static_lds_bytes
 
 
 # ---------------------------------------------------------------- the launch table
-# (LANE, QUADS, TALLY, CAM) -> None (reachable) or why no public call reaches it.
+# (LANE, QUADS, TALLY, CAM, TRIS, CSG) -> None (reachable) or why no public call reaches it.
+CLASSES = ((False, False, False), (True, False, False), (True, True, False), (True, True, True))  # (QUADS, TRIS, CSG)
+
+
 def _launch_table():
     t = {}
-    for quads in (False, True):
+    for quads, tris, csg in CLASSES:  # (launch_fused: TRIS and CSG force QUADS, CSG forces TRIS)
         for tally in (False, True):
-            t[(0, quads, tally, True)] = None  # the wave traversal only ever takes camera rays
+            t[(0, quads, tally, True, tris, csg)] = None  # the wave traversal only ever takes camera rays
             for lane in (15, 14, 4, 3, 1):
                 for cam in (False, True):
-                    t[(lane, quads, tally, cam)] = None
+                    # (LANE 3 and 1 with CAM and TRIS or CSG: a scene without diagonal spheres whose fused
+                    # generations the triangles' or the grouped spheres' hierarchy opens: mesh_nodiag, csg_nodiag)
+                    t[(lane, quads, tally, cam, tris, csg)] = None
     for tally in (False, True):
         for lane in (3, 1):
-            t[(lane, False, tally, True)] = (
+            t[(lane, False, tally, True, False, False)] = (
                 "generation 0 of a camera render takes LANE 3 or 1 only in a scene without diagonal spheres "
                 "(with them wf_plan_image sends it to LANE 0: lane_prim needs an LDS or four-wide image); such a "
                 "scene is fused only through the other records' or the lines' hierarchy, which sets QUADS")
@@ -99,7 +128,9 @@ def _launch_table():
 
 
 LAUNCH_TABLE = _launch_table()
-assert len(LAUNCH_TABLE) == 44  # launch_fused_q: 4 + 2 x 8; launch_glb_lane: 3 x 8
+# launch_fused_q: 4 + 2 x 8, launch_glb_lane: 3 x 8 (44); with TRIS 2 + 2 x 4 and 3 x 4 (22); with TRIS, CSG as many
+assert len(LAUNCH_TABLE) == 88
+assert [sum(1 for t in LAUNCH_TABLE if (t[1], t[4], t[5]) == c) for c in CLASSES] == [22, 22, 22, 22]
 
 # ---------------------------------------------------------------- the knob rows
 # name, knobs, lane of the deeper generations, n_top ("wide": n_bvh_wide, "bin": n_bvh_nodes, 0), distances staged
@@ -316,8 +347,170 @@ def _light_field(rt, n, n_lights, seed=53):
     return w, cam, 2
 
 
+# ---- the scenes of the TRIS and CSG classes: 24x16, depth 3, two lights (one off the camera's axis)
+W2, H2, DEPTH2 = 24, 16, 3
+
+
+def _two_lights(rt, w):
+    w.add_light(rt.PointLight(rt.Point(-6, 8, -8), rt.Color(1, 1, 1)))
+    w.add_light(rt.PointLight(rt.Point(5, 6, -4), rt.Color(0.35, 0.35, 0.35)))
+
+
+def _camera2(rt, frm=(0.0, 2.0, -6.0), to=(0.0, 0.6, 0.0)):
+    cam = rt.Camera(W2, H2, PI / 3)
+    cam.set_transform(rt.view_transform(rt.Point(*frm), rt.Point(*to), rt.Vector(0, 1, 0)))
+    return cam
+
+
+def _diag_spheres(rt, w, xs=(-2.1, 2.1)):
+    """Two diagonal glass spheres: what makes test_gpu_csg.py's scene (a) reach all five images."""
+    for x, idx in zip(xs, (1.5, 1.33)):
+        s = rt.glass_sphere()
+        s.set_transform(rt.translation(x, 0.7, 0.4) * rt.scaling(0.7, 0.7, 0.7))
+        s.material.refractive_index = idx
+        s.material.reflective = 0.4
+        w.add_object(s)
+
+
+def _torus(rt, n, smooth, place, transparent=False):
+    """scenes.mesh_torus(n, n) as one group (2 n n triangles), divided, then rotated and scaled non-uniformly."""
+    from rtamd import scenes
+    g = rt.parse_obj_string(scenes.mesh_torus(n, n, smooth)).as_group()
+    m = rt.Material()
+    m.color = rt.Color(0.9, 0.45, 0.2)
+    m.reflective = 0.15
+    if transparent:
+        m.transparency = 0.3
+        m.refractive_index = 1.3
+    g.set_material(m)
+    g.divide(4)
+    g.set_transform(place * rt.rotation_x(0.6) * rt.rotation_z(0.3) * rt.scaling(1.2, 0.9, 1.0))
+    return g
+
+
+def _floor(rt, patterned=False):
+    floor = rt.Plane()
+    floor.material.reflective = 0.3
+    floor.material.color = rt.Color(0.8, 0.8, 0.7)
+    if patterned:
+        p = rt.ring_pattern(rt.Color(0.8, 0.8, 0.7), rt.Color(0.3, 0.4, 0.5))
+        p.set_transform(rt.translation(0.2, 0.0, 0.3) * rt.scaling(0.8, 1.0, 0.6))
+        floor.material.set_pattern(p)
+    return floor
+
+
+def _die(rt, place, color, patterned):
+    """scenes.csg_die's tree, (cube & sphere) - (three cylinders), with a checkers pattern on the cube leaf."""
+    m = rt.Material()
+    m.color = rt.Color(*color)
+    m.reflective = 0.2
+    cube = rt.Cube()
+    cube.set_transform(place)
+    cube.set_material(m)
+    if patterned:
+        p = rt.checkers_pattern(rt.Color(0.9, 0.9, 0.9), rt.Color(0.2, 0.1, 0.5))
+        p.set_transform(rt.scaling(0.5, 0.5, 0.5))
+        cube.material.set_pattern(p)
+    ball = rt.Sphere()
+    ball.set_transform(place * rt.scaling(1.38, 1.38, 1.38))
+    ball.set_material(m)
+    body = rt.Csg(rt.Operation.Intersection, cube, ball)
+    drills = []
+    for turn in (rt.rotation_z(PI / 2.0), None, rt.rotation_x(PI / 2.0)):
+        c = rt.Cylinder(-1.5, 1.5, True)
+        c.set_transform((place * turn if turn is not None else place) * rt.scaling(0.35, 1.0, 0.35))
+        c.set_material(m)
+        drills.append(c)
+    holes = rt.Csg(rt.Operation.Union, drills[0], rt.Csg(rt.Operation.Union, drills[1], drills[2]))
+    return rt.Csg(rt.Operation.Difference, body, holes)
+
+
+def _mesh(rt):
+    w = rt.World()
+    w.add_object(_floor(rt))
+    _diag_spheres(rt, w)
+    w.add_object(_torus(rt, 6, True, rt.translation(0.0, 1.1, 0.0), transparent=True))
+    fin = rt.Triangle(rt.Point(-2.6, 0.0, -0.5), rt.Point(-1.6, 0.0, -1.4), rt.Point(-2.0, 1.8, -0.8))
+    fin.material.color = rt.Color(0.2, 0.6, 0.9)
+    fin.no_shadow()
+    w.add_object(fin)
+    cube = rt.Cube()
+    cube.set_transform(rt.translation(1.3, 0.4, -1.6) * rt.rotation_y(0.5) * rt.scaling(0.4, 0.4, 0.4))
+    cube.material.color = rt.Color(0.3, 0.8, 0.3)
+    cube.material.reflective = 0.3
+    w.add_object(cube)
+    g = rt.Group()  # a patterned triangle group: a flat and a smooth triangle under one striped material
+    g.add_child(rt.Triangle(rt.Point(-1.2, 0.0, -2.0), rt.Point(-0.2, 0.0, -2.2), rt.Point(-0.7, 1.0, -1.9)))
+    g.add_child(rt.SmoothTriangle(rt.Point(-0.2, 0.0, -2.2), rt.Point(0.6, 0.0, -1.8), rt.Point(0.2, 0.9, -2.0),
+                                  rt.Vector(-0.3, 0.1, -1.0), rt.Vector(0.3, 0.1, -1.0), rt.Vector(0.0, 0.5, -1.0)))
+    m = rt.Material()
+    p = rt.stripe_pattern(rt.Color(0.9, 0.9, 0.2), rt.Color(0.2, 0.2, 0.9))
+    p.set_transform(rt.rotation_z(0.5) * rt.scaling(0.15, 0.15, 0.15))
+    m.set_pattern(p)
+    g.set_material(m)
+    w.add_object(g)
+    _two_lights(rt, w)
+    return w, _camera2(rt), DEPTH2
+
+
+def _mesh_nodiag(rt):
+    w = rt.World()
+    w.add_object(_floor(rt))
+    w.add_object(_torus(rt, 6, False, rt.translation(-0.3, 1.1, 0.0)))
+    cone = rt.Cone()  # unbounded: outside every hierarchy, so the triangles' is the only one
+    cone.set_transform(rt.translation(2.2, 1.2, 0.3) * rt.rotation_z(0.3) * rt.scaling(0.15, 1.0, 0.15))
+    cone.material.color = rt.Color(0.2, 0.5, 0.9)
+    cone.material.reflective = 0.4
+    w.add_object(cone)
+    _two_lights(rt, w)
+    return w, _camera2(rt), DEPTH2
+
+
+def _csg(rt):
+    w = rt.World()
+    w.add_object(_floor(rt))
+    w.add_object(_die(rt, rt.translation(0.0, 0.8, 0.0) * rt.rotation_y(0.6) * rt.scaling(0.8, 0.8, 0.8), (0.9, 0.3, 0.2), True))
+    _diag_spheres(rt, w)
+    _two_lights(rt, w)
+    return w, _camera2(rt, to=(0.0, 0.5, 0.0)), DEPTH2
+
+
+def _csg_nodiag(rt):
+    import test_gpu_csg
+    w, _, _ = test_gpu_csg._scene_b(rt)  # a transformed Csg, a Csg in a divided group, a group in a Csg; two lights
+    return w, _camera2(rt, (0.0, 2.5, -7.0), (0.0, 0.5, 0.0)), DEPTH2
+
+
+def _mixed(rt):
+    w = rt.World()
+    w.add_object(_floor(rt, patterned=True))
+    w.add_object(_die(rt, rt.translation(-1.9, 0.7, -0.6) * rt.rotation_y(0.4) * rt.scaling(0.6, 0.6, 0.6), (0.9, 0.3, 0.2), False))
+    g = rt.Group()  # a divided 32-triangle mesh in one group with a second Csg
+    g.add_child(_torus(rt, 4, True, rt.translation(0.2, 1.2, 0.4), transparent=True))
+    a = rt.Sphere()
+    a.set_transform(rt.translation(1.4, 0.6, -0.9) * rt.scaling(0.6, 0.6, 0.6))
+    a.material.color = rt.Color(0.2, 0.8, 0.3)
+    b = rt.Cube()
+    b.set_transform(rt.translation(1.7, 0.8, -1.1) * rt.rotation_y(0.3) * rt.scaling(0.4, 0.4, 0.4))
+    b.material.transparency = 0.8
+    b.material.refractive_index = 1.4
+    b.material.reflective = 0.3
+    g.add_child(rt.Csg(rt.Operation.Difference, a, b))
+    w.add_object(g)
+    _diag_spheres(rt, w, xs=(-0.4, 2.9))
+    can = rt.Cylinder(0.0, 1.0, True)
+    can.set_transform(rt.translation(-3.2, 0.0, 1.2) * rt.scaling(0.5, 1.3, 0.5))
+    can.material.color = rt.Color(0.7, 0.7, 0.2)
+    can.material.reflective = 0.3
+    w.add_object(can)
+    _two_lights(rt, w)
+    return w, _camera2(rt, (0.0, 2.4, -6.5)), DEPTH2
+
+
+NEW_SCENES = ("mesh", "mesh_nodiag", "csg", "csg_nodiag", "mixed")  # the checker of tests/csg_ref.py is their yardstick
 SCENES = {f"fuzz{s}": s for s in FUZZ_SEEDS}
 SCENES.update(cluster=_ellipsoid_cluster, solids=_solids_only, planes=_two_planes)
+SCENES.update(mesh=_mesh, mesh_nodiag=_mesh_nodiag, csg=_csg, csg_nodiag=_csg_nodiag, mixed=_mixed)
 # What the profile must show of each scene: n_quads, n_other_culled, n_line_culled, n_gen, n_lights, n_planes
 # (the fuzz generator makes at most 13 solids, below the line hierarchy's 16 records: n_line_culled
 # is 0 there, and it replaces every unbounded cylinder or cone; `solids` has both).
@@ -331,6 +524,13 @@ SCENE_PROFILE = {
     "cluster": dict(n_quads=0, n_lights=2, n_planes=1, n_gen=0, n_other_culled=0, n_line_culled=0, n_diag=250),
     "solids": dict(n_lights=2, n_planes=1, n_diag=0),
     "planes": dict(n_quads=0, n_lights=2, n_planes=2, n_diag=0, n_gen=0),
+    "mesh": dict(n_lights=2, n_planes=1, n_diag=2, n_gen=0, n_quads=1, n_bvh_nodes=1, n_obvh_nodes=0, n_lbvh_nodes=0),
+    # (no hierarchy but the triangles': theirs alone opens the fused generations)
+    "mesh_nodiag": dict(n_lights=2, n_planes=1, n_diag=0, n_gen=0, n_quads=1, n_bvh_nodes=0, n_obvh_nodes=0, n_lbvh_nodes=0),
+    "csg": dict(n_lights=2, n_planes=1, n_diag=2, n_gen=0, n_quads=0, n_bvh_nodes=1),
+    # (the four grouped spheres' hierarchy opens the fused generations)
+    "csg_nodiag": dict(n_lights=2, n_planes=1, n_diag=0, n_gen=4, n_other_culled=4, n_bvh_nodes=0, n_obvh_nodes=1),
+    "mixed": dict(n_lights=2, n_planes=1, n_diag=2, n_gen=0, n_quads=1, n_bvh_nodes=1),
 }
 
 
@@ -345,6 +545,15 @@ def _quads(prof):
     return prof["n_quads"] > 0 or prof["n_obvh_nodes"] > 0 or prof["n_lbvh_nodes"] > 0
 
 
+def _tris_csg(w):
+    """launch_fused's TRIS and CSG restated from the world's own records: CSG, the world
+    holds a Csg node; TRIS, it holds triangles and no Csg."""
+    import csg_ref
+    csg = bool((np.frombuffer(w.nodes_bytes(), dtype=csg_ref.NODE)["kind"] == csg_ref.NODE_CSG).any())
+    tris = len(w.triangles_bytes()) > 0 and not csg
+    return tris or csg, csg  # (the Csg kernels are triangle kernels: wf_trace_fused<.., TRIS = true, CSG = true>)
+
+
 def _rays(seed, n=2000):
     rng = np.random.default_rng(seed)
     o = rng.uniform([-4.5, -0.2, -2.5], [4.5, 3.5, 6.5], size=(n, 3))  # test_gpu_fuzz.py's volume: many inside shapes
@@ -355,7 +564,7 @@ def _rays(seed, n=2000):
 
 class _Sweep:
     """One scene through every variant and mode; the failures as text, the
-    (LANE, QUADS, TALLY, CAM) tuples the asserted readouts show were launched."""
+    (LANE, QUADS, TALLY, CAM, TRIS, CSG) tuples the asserted readouts show were launched."""
 
     def __init__(self, rt, oracle, name):
         from rtamd import scenes
@@ -368,9 +577,19 @@ class _Sweep:
         exh, self.st = cam.render(w, depth)
         self.frame = exh.to_numpy()
         self.prof = _prof(rt, w)
-        self.quads = _quads(self.prof)
+        self.tris, self.csg = _tris_csg(w)
+        self.tri_plan = rt._rtamd._wf_plan(w)["triangles"]  # (of the scene: the hierarchy's records, depth, nodes)
+        self.quads = _quads(self.prof) or self.tris  # (TRIS and CSG force QUADS)
         self.check(self.prof["bvh_depth"] <= K_LANE_LDS_DEPTH, "a tree too deep for LANE 3")  # (else LANE 1)
-        ref, rst = oracle.OracleWorld.from_world(w).render(cam.desc_bytes(), depth, nthreads=NTHREADS)
+        if name in NEW_SCENES:  # the oracle refuses triangles and Csg
+            import csg_ref
+            checker = csg_ref.CsgRef.from_world(w)
+            ref, rst = checker.render(cam.desc_bytes(), depth)
+            self.check(checker.csg_ties == 0, f"{checker.csg_ties} equal-t pairs in a Csg node's list")
+            self.check(self.tris, "neither a triangle nor a Csg")
+        else:
+            ref, rst = oracle.OracleWorld.from_world(w).render(cam.desc_bytes(), depth, nthreads=NTHREADS)
+            self.check(not self.tris and not self.csg, "a triangle or a Csg")
         self.check(np.isfinite(self.frame).all(), "exhaustive frame not finite")
         self.check(self.frame.tobytes() == ref.tobytes(), f"exhaustive != oracle in {int((self.frame != ref).sum())} channels")
         self.check(rt.canvas_to_ppm(self.frame) == oracle.canvas_to_ppm(ref), "PPM bytes differ from the oracle's")
@@ -379,11 +598,12 @@ class _Sweep:
         self.aa_cam = (scenes.fuzz(mk, 64, 48) if isinstance(mk, int) else mk(rt))[1]
         self.aa_cam.render_opts.aa_samples(rt.AASamples.X4)
         self.frame4 = self.aa_cam.render_multithreaded(w, depth)[0].to_numpy().tobytes()
-        self.rays = _rays(len(name) + 7 * depth)
+        self.rays = _rays(len(name) + 7 * depth, 400 if name in NEW_SCENES else 2000)
         self.batch0 = w.color_at_batch(self.rays, 0, True, True)
         self.batch = w.color_at_batch(self.rays, depth, True, True)
         self.frame = self.frame.tobytes()
-        self.fused = self.prof["n_bvh_nodes"] > 0 or self.prof["n_obvh_nodes"] > 0 or self.prof["n_lbvh_nodes"] > 0
+        self.fused = self.prof["n_bvh_nodes"] > 0 or self.prof["n_obvh_nodes"] > 0 or self.prof["n_lbvh_nodes"] > 0 or \
+            self.tri_plan["nodes"] > 0
         for vname, knobs, lane, n_top, deltas in _variants():
             try:
                 _tune(w, knobs)
@@ -399,6 +619,10 @@ class _Sweep:
     def plan(self, what, knobs, lane, n_top, deltas, camera, tally, deeper):
         """Asserts the plan readout of the render just made and records its launches."""
         p = self.rt._rtamd._wf_plan(self.w)
+        # what launch_fused chooses the class by, against the world's own records
+        self.check((p["n_csg_units"] > 0) == self.csg and (p["n_tris"] > 0 or self.csg) == self.tris,
+                   f"{what}: n_tris {p['n_tris']}, n_csg_units {p['n_csg_units']} for TRIS {self.tris} CSG {self.csg}")
+        self.check(p["triangles"]["ran"] == (self.fused and self.tri_plan["nodes"] > 0), f"{what}: triangles {p['triangles']}")
         if not self.fused:
             self.check(p["primary"]["lane"] == -1 and p["secondary"]["lane"] == -1, f"{what}: a fused launch {p}")
             return
@@ -412,7 +636,7 @@ class _Sweep:
             ok = ok and got["dyn"] + _static_lds(wl) <= K_FUSED_LDS_LIMIT and (got["dyn"] > 0 or wl in (3, 1))
             self.check(ok, f"{what}: {which} plan {got}, expected lane {wl} n_top {wt} deltas {wd} spheres {ws}")
             if ok:
-                self.reached.add((wl, self.quads, tally, cam_rays or wl == 0))
+                self.reached.add((wl, self.quads, tally, cam_rays or wl == 0, self.tris, self.csg))
 
     def variant(self, vname, knobs, lane, n_top, deltas):
         w, cam, depth = self.w, self.cam, self.depth
@@ -463,7 +687,16 @@ def test_variants_bitwise(sweep, name):
         assert not s.fused and not s.reached
         return
     assert s.fused and s.prof["n_lights"] >= 2 and s.depth >= 3
-    if name == "solids":
+    if name in NEW_SCENES:
+        assert (s.tris, s.csg) == {"mesh": (True, False), "mesh_nodiag": (True, False)}.get(name, (True, True))
+        assert (s.cam.hsize, s.cam.vsize, s.depth, len(s.rays)) == (W2, H2, DEPTH2, 400)
+        n_tri = len(s.w.triangles_bytes()) // 144
+        assert n_tri == {"mesh": 75, "mesh_nodiag": 72, "mixed": 32}.get(name, 0)
+        # every mesh: at least 16 boxed triangles, so the walk (tri_trace) ran, not the remainder's loop
+        assert s.tri_plan["records"] == n_tri and (n_tri == 0 or (s.tri_plan["nodes"] > 0 and 0 < s.tri_plan["depth"] <= 60))
+        assert s.st["rays_reflect"] > 20 and s.st["rays_refract"] > (-1 if name == "mesh_nodiag" else 20)
+        assert s.st["other_tests"] > 0 and _features(s.w)["patterns"] == {"mesh": 2, "csg": 1, "mixed": 1}.get(name, 0)
+    elif name == "solids":
         assert s.quads and s.prof["n_other_culled"] >= 16 and s.prof["n_line_culled"] >= 16
         assert s.prof["n_quads"] > s.prof["n_other_culled"] + s.prof["n_line_culled"] - s.prof["n_gen"]  # unbounded ones
         f = _features(s.w)
@@ -517,20 +750,21 @@ def test_fuzz_seeds_hold_every_feature(rt):
     assert sum(tot["unbounded"]) == 0  # (scenes.fuzz keeps none: the `solids` scene has them)
 
 
-@pytest.mark.parametrize("quads", [False, True])
-def test_every_reachable_kernel_variant_ran(sweep, quads):
+@pytest.mark.parametrize("quads,tris,csg", CLASSES, ids=["plain", "quads", "tris", "csg"])
+def test_every_reachable_kernel_variant_ran(sweep, quads, tris, csg):
     """Completeness: the asserted plan readouts of the sweep cover every
-    (LANE, QUADS, TALLY, CAM) instantiation the launch switch can produce,
-    except those LAUNCH_TABLE explains as unreachable."""
+    (LANE, QUADS, TALLY, CAM, TRIS, CSG) instantiation the launch switch can
+    produce, except those LAUNCH_TABLE explains as unreachable."""
     reached = set()
     for name in sorted(SCENES):
         reached |= sweep(name).reached
     assert reached <= set(LAUNCH_TABLE), reached - set(LAUNCH_TABLE)
-    want = {t for t, why in LAUNCH_TABLE.items() if t[1] == quads and why is None}
+    mine = lambda t: (t[1], t[4], t[5]) == (quads, tris, csg)
+    want = {t for t, why in LAUNCH_TABLE.items() if mine(t) and why is None}
     assert len(want) == (22 if quads else 18)
     missing = want - reached
     assert not missing, sorted(missing)
-    unreachable = {t for t, why in LAUNCH_TABLE.items() if t[1] == quads and why is not None}
+    unreachable = {t for t, why in LAUNCH_TABLE.items() if mine(t) and why is not None}
     assert not (unreachable & reached), sorted(unreachable & reached)
 
 

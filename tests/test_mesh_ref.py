@@ -6,6 +6,10 @@ shadow answers and counters equal liboracle's bit for bit; the oracle is itself
 pinned by the reference's KATs.
 Pin 2: the reference's triangle KATs (triangle.rs:105-210,
 smooth_triangle.rs:113-200) through the checker's triangle functions.
+Pin 3: patterns. A sphere-and-plane world with all five pattern kinds, with
+and without a pattern transform, equals liboracle's frame and counters bit for
+bit; the reference's pattern KATs (stripe.rs, gradient.rs, ring.rs,
+checkers.rs, test_pattern.rs) with their own expected colours.
 """
 import math
 import random
@@ -144,9 +148,10 @@ def test_checker_refuses_what_it_does_not_restate(rt):
     with pytest.raises(ValueError):
         mesh_ref.MeshRef.from_world(w)
     w = rt.World()
-    s = rt.Sphere()
-    s.material.set_pattern(rt.stripe_pattern(rt.Color(1, 1, 1), rt.Color(0, 0, 0)))
-    w.add_object(s)
+    w.add_object(rt.Sphere())
+    c = rt.Cube()
+    c.material.set_pattern(rt.stripe_pattern(rt.Color(1, 1, 1), rt.Color(0, 0, 0)))
+    w.add_object(c)
     with pytest.raises(ValueError):
         mesh_ref.MeshRef.from_world(w)
 
@@ -210,3 +215,114 @@ def test_kat_smooth_triangle_interpolates_the_normal(rt):  # smooth_triangle.rs:
     # ... and the intersection the checker itself finds carries that u and v
     xs = ref.intersect((-0.2, 0.3, -2.0), (0.0, 0.0, 1.0))
     assert len(xs) == 1 and abs(xs[0][2] - 0.45) < mesh_ref.EPSILON and abs(xs[0][3] - 0.25) < mesh_ref.EPSILON
+
+
+# ---- Pin 3: patterns
+def _patterned_world(rt):
+    rnd = random.Random(5)
+    a, b = rt.Color(0.9, 0.2, 0.1), rt.Color(0.1, 0.3, 0.8)
+    makes = [rt.test_pattern, lambda: rt.stripe_pattern(a, b), lambda: rt.gradient_pattern(a, b),
+             lambda: rt.ring_pattern(a, b), lambda: rt.checkers_pattern(a, b)]
+    w = rt.World()
+    floor = rt.Plane()
+    p = rt.checkers_pattern(rt.Color(0.9, 0.9, 0.9), rt.Color(0.2, 0.2, 0.2))
+    p.set_transform(rt.rotation_y(0.3) * rt.scaling(0.7, 0.7, 0.7))
+    floor.material.set_pattern(p)
+    floor.material.reflective = 0.3
+    w.add_object(floor)
+    wall = rt.Plane()
+    wall.set_transform(rt.translation(0, 0, 5) * rt.rotation_x(math.pi / 2))
+    wall.material.set_pattern(rt.ring_pattern(a, b))
+    w.add_object(wall)
+    for k in range(10):  # every kind without and with its own transform
+        s = rt.Sphere()
+        s.set_transform(rt.translation(-3.2 + 1.4 * (k % 5), 0.7 + 1.5 * (k // 5), 0.5 * (k // 5)) * rt.rotation_z(0.2 * k)
+                        * rt.scaling(0.6, 0.5 + 0.05 * k, 0.6))
+        p = makes[k % 5]()
+        if k >= 5:
+            p.set_transform(rt.translation(0.1, 0.2, 0.3) * rt.rotation_y(rnd.uniform(0, 3)) * rt.scaling(0.3, 0.25, 0.2))
+        s.material.set_pattern(p)
+        if k in (2, 8):
+            s.material.transparency = 0.6
+            s.material.refractive_index = 1.4
+        if k == 4:
+            s.material.reflective = 0.4
+        w.add_object(s)
+    w.add_light(rt.PointLight(rt.Point(-6, 8, -8), rt.Color(0.9, 0.9, 0.9)))
+    w.add_light(rt.PointLight(rt.Point(4, 5, -3), rt.Color(0.3, 0.3, 0.4)))
+    cam = rt.Camera(24, 16, math.pi / 3)
+    cam.set_transform(rt.view_transform(rt.Point(0.2, 2.0, -6.0), rt.Point(0, 1.2, 0), rt.Vector(0, 1, 0)))
+    return w, cam
+
+
+def test_checker_patterned_frame_and_counters_equal_the_oracle_bitwise(rt, oracle):
+    w, cam = _patterned_world(rt)
+    d = np.frombuffer(w.descs_bytes(), dtype=mesh_ref.SHAPE)
+    ident = np.eye(4).ravel()
+    cover = {(int(k), bool((t != ident).any())) for k, t in zip(d["pattern_kind"], d["pattern_transform"])}
+    assert cover >= {(k, t) for k in range(5) for t in (False, True)} and set(d["kind"]) == {0, 1}
+    ref = mesh_ref.MeshRef.from_world(w)
+    img, st = ref.render(cam.desc_bytes(), 3)
+    oimg, ost = oracle.OracleWorld.from_world(w).render(cam.desc_bytes(), 3)
+    assert img.tobytes() == oimg.tobytes(), np.abs(img - oimg).max()
+    assert st == {k: ost[k] for k in st}
+    assert st["rays_reflect"] > 0 and st["rays_refract"] > 0
+    assert len(np.unique(img.reshape(-1, 3), axis=0)) > 100
+
+
+WHITE, BLACK = (1.0, 1.0, 1.0), (0.0, 0.0, 0.0)
+
+
+@pytest.mark.parametrize("kind,cases", [
+    (mesh_ref.PATTERN_STRIPE, [((0, 0, 0), WHITE), ((0, 1, 0), WHITE), ((0, 2, 0), WHITE),       # stripe.rs: constant in y
+                               ((0, 0, 1), WHITE), ((0, 0, 2), WHITE),                           # constant in z
+                               ((0.9, 0, 0), WHITE), ((1, 0, 0), BLACK), ((-0.1, 0, 0), BLACK),  # alternates in x
+                               ((-1, 0, 0), BLACK), ((-1.1, 0, 0), WHITE)]),
+    (mesh_ref.PATTERN_GRADIENT, [((0, 0, 0), WHITE), ((0.25, 0, 0), (0.75, 0.75, 0.75)), ((0.5, 0, 0), (0.5, 0.5, 0.5)),
+                                 ((0.75, 0, 0), (0.25, 0.25, 0.25))]),                           # gradient.rs
+    (mesh_ref.PATTERN_RING, [((0, 0, 0), WHITE), ((1, 0, 0), BLACK), ((0, 0, 1), BLACK),
+                             ((0.708, 0, 0.708), BLACK)]),                                       # ring.rs
+    (mesh_ref.PATTERN_CHECKERS, [((0, 0, 0), WHITE), ((0.99, 0, 0), WHITE), ((1.01, 0, 0), BLACK),  # checkers.rs: x, y, z
+                                 ((0, 0.99, 0), WHITE), ((0, 1.01, 0), BLACK), ((0, 0, 0.99), WHITE),
+                                 ((0, 0, 1.01), BLACK)])], ids=["stripe", "gradient", "ring", "checkers"])
+def test_kat_pattern_color_at(kind, cases):
+    for p, want in cases:
+        got = mesh_ref.pattern_color_at(kind, WHITE, BLACK, tuple(float(x) for x in p))
+        assert _eq(got, want), (p, got)  # Color's PartialEq: within EPSILON
+
+
+def test_kat_pattern_color_at_where_rust_and_python_differ():
+    """`%` on an f64 keeps the dividend's sign (fmod); `as isize` saturates and sends a NaN to 0."""
+    assert mesh_ref.pattern_color_at(mesh_ref.PATTERN_STRIPE, WHITE, BLACK, (-3.0, 0.0, 0.0)) == BLACK  # -3 % 2 == -1
+    assert mesh_ref.pattern_color_at(mesh_ref.PATTERN_STRIPE, WHITE, BLACK, (float("inf"), 0.0, 0.0)) == BLACK  # NaN
+    assert mesh_ref.pattern_color_at(mesh_ref.PATTERN_CHECKERS, WHITE, BLACK, (float("nan"), 0.0, 0.0)) == WHITE
+    assert mesh_ref.pattern_color_at(mesh_ref.PATTERN_CHECKERS, WHITE, BLACK, (1e300, 0.0, 0.0)) == BLACK  # isize::MAX
+    assert mesh_ref.pattern_color_at(mesh_ref.PATTERN_CHECKERS, WHITE, BLACK, (-1e300, 0.0, 0.0)) == WHITE  # isize::MIN
+    assert mesh_ref.pattern_color_at(mesh_ref.PATTERN_CHECKERS, WHITE, BLACK, (-0.5, 0.0, 0.0)) == BLACK
+
+
+@pytest.mark.parametrize("shape_t,pattern_t,point,want", [
+    ((2, 2, 2), None, (2, 3, 4), (1.0, 1.5, 2.0)),                 # test_pattern.rs: an object transformation
+    (None, ("s", 2, 2, 2), (2, 3, 4), (1.0, 1.5, 2.0)),            # a pattern transformation
+    ((2, 2, 2), ("t", 0.5, 1.0, 1.5), (2.5, 3.0, 3.5), (0.75, 0.5, 0.25))])  # both
+def test_kat_pattern_with_object_and_pattern_transformation(rt, shape_t, pattern_t, point, want):
+    """Through the matrices of the library's own records, as `lighting` reads them."""
+    s = rt.Sphere()
+    if shape_t:
+        s.set_transform(rt.scaling(*shape_t))
+    p = rt.test_pattern()
+    if pattern_t:
+        p.set_transform((rt.scaling if pattern_t[0] == "s" else rt.translation)(*pattern_t[1:]))
+    s.material.set_pattern(p)
+    w = rt.World()
+    w.add_object(s)
+    d = np.frombuffer(w.descs_bytes(), dtype=mesh_ref.SHAPE)[0]
+    got = mesh_ref.pattern_color_at_shape(int(d["pattern_kind"]), None, None, [float(x) for x in d["pattern_inverse"]],
+                                          [float(x) for x in d["inverse"]], tuple(float(x) for x in point))
+    assert _eq(got, want), got
+    # ... and `lighting` takes that colour: ambient 1 under a white light in shadow gives it back
+    d = d.copy()
+    d["ambient"] = 1.0
+    ref = mesh_ref.MeshRef(d.tobytes())
+    L = np.array([0.0, 10.0, 0.0, 1.0, 1.0, 1.0])
+    assert _eq(ref.lighting(0, L, tuple(float(x) for x in point), (0.0, 0.0, -1.0), (0.0, 0.0, -1.0), True), want)
