@@ -87,6 +87,7 @@ extern "C" int rtamd_nccl_comm_destroy(void* comm);
 extern "C" int rtamd_wf_profile(const rt_scene* s, int enable, double out[40]);
 extern "C" int rtamd_wf_gen_counts(const rt_scene* s, unsigned* out, int max);
 extern "C" int rtamd_wf_plan(const rt_scene* s, long long out[14]);
+extern "C" int rtamd_csg_plan(const rt_scene* s, long long out[6]);
 extern "C" int rtamd_scene_tuning_set(const rt_scene* s, const char* key, int value);
 extern "C" int rtamd_render_shard_host(const rt_scene* scene, const rt_camera_desc* camera, uint32_t max_depth,
                                        uint32_t aa_samples, uint32_t row_block, uint32_t shard, uint32_t n_shards,
@@ -820,6 +821,16 @@ PYBIND11_MODULE(_rtamd, m) {
     d["triangles"] = t;
     d["n_tris"] = o[12];  // what launch_fused chooses the TRIS and CSG kernels by
     d["n_csg_units"] = o[13];
+    return d;
+  }, py::arg("world"));
+  // the Csg units' hierarchy (unit_trace): the scene's units, those the hierarchy holds, those left
+  // to the loop, its nodes and depth; `ran` = the last render walked it
+  m.def("_csg_plan", [](const World& w) {
+    long long o[6] = {0};
+    check(rtamd_csg_plan(w.scene(), o), "csg_plan");
+    py::dict d;
+    d["units"] = o[0]; d["records"] = o[1]; d["remainder"] = o[2];
+    d["nodes"] = o[3]; d["depth"] = o[4]; d["ran"] = o[5] != 0;
     return d;
   }, py::arg("world"));
   m.def("_tuning_set", [](const std::string& k, int v) { check(rtamd_tuning_set(k.c_str(), v), "tuning"); });

@@ -15,6 +15,10 @@ int g_bvh_ct = 70;      // SAH node-visit cost in percent of a sphere test (tuni
 // light-buffer cells per cube-map face edge at scene creation ("lb_res"): 0 = none, -1 = by
 // scene size (256, or 512 above 4096 diagonal spheres: C5 47.1 -> 46.7 ms/frame, C3 unchanged)
 int g_lb_res = -1;
+// boxed Csg units from which the unit hierarchy is built ("csg_hier_min"; 0 restores the default,
+// the other hierarchies' kMinHierRecords; profiles/csg_hier_ab.txt)
+constexpr int kCsgHierMinDefault = 16;
+int g_csg_hier_min = kCsgHierMinDefault;
 std::mutex g_tune_mu;
 WfTuning g_tune_defaults;
 
@@ -145,6 +149,24 @@ int rtamd_wf_plan(const rt_scene* cs, long long out[14]) {
   return RT_OK;
 }
 
+// Development hook (not in the public ABI): the Csg units' hierarchy (unit_trace). out[0..5]: the
+// scene's units, the boxed units the hierarchy holds, the units left to the loop, the hierarchy's
+// nodes and depth, and whether the last render walked it (a fused render of a scene that has one).
+int rtamd_csg_plan(const rt_scene* cs, long long out[6]) {
+  if (!cs || !out) return fail(RT_ERR_INVALID_ARGUMENT, "null scene or output");
+  rt_scene* s = const_cast<rt_scene*>(cs);
+  std::lock_guard<std::mutex> lk(s->mu);
+  const bool fused =
+      s->last_wf && (s->last_wf->wf->plan_primary().lane >= 0 || s->last_wf->wf->plan_secondary().lane >= 0);
+  out[0] = s->dev.n_csg_units;
+  out[1] = s->dev.n_ubvh > 0 ? s->dev.n_urec : 0;
+  out[2] = s->dev.n_fx_units;
+  out[3] = s->dev.n_ubvh;
+  out[4] = s->dev.ubvh_depth;
+  out[5] = s->dev.n_ubvh > 0 && fused ? 1 : 0;
+  return RT_OK;
+}
+
 // Rays of each generation of the scene's last render (dev tool): returns the
 // number of generations written into out[0 .. max).
 int rtamd_wf_gen_counts(const rt_scene* cs, unsigned* out, int max) {
@@ -161,7 +183,7 @@ int rtamd_wf_gen_counts(const rt_scene* cs, unsigned* out, int max) {
 }
 
 // Development-only tuning hooks (not declared in include/rt_render.h).
-// rtamd_tuning_set: the scene-creation knobs (lb_res, bvh_leaf, bvh_ct) and
+// rtamd_tuning_set: the scene-creation knobs (lb_res, bvh_leaf, bvh_ct, csg_hier_min) and
 // the render-time defaults copied into scenes created afterwards;
 // rtamd_scene_tuning_set: one scene's render-time knobs (WfTuning).
 int rtamd_tuning_set(const char* key, int value) {
@@ -179,6 +201,12 @@ int rtamd_tuning_set(const char* key, int value) {
   if (key && std::strcmp(key, "bvh_leaf") == 0) {
     if (value < 0 || value > kBvhLeafMax) return fail(RT_ERR_INVALID_ARGUMENT, "bvh_leaf must be in [0, 127]");
     g_bvh_leaf = value;
+    return RT_OK;
+  }
+  if (key && std::strcmp(key, "csg_hier_min") == 0) {
+    if (value < 0 || value > 65536)
+      return fail(RT_ERR_INVALID_ARGUMENT, "csg_hier_min must be in [1, 65536], or 0 for the default");
+    g_csg_hier_min = value ? value : kCsgHierMinDefault;
     return RT_OK;
   }
   std::lock_guard<std::mutex> lk(g_tune_mu);

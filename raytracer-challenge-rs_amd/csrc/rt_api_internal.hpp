@@ -49,6 +49,7 @@ extern thread_local std::string g_err;  // rt_last_error's text (rt_api.cpp)
 extern int g_bvh_leaf;  // BVH leaf size; 0 = automatic: 2, or 1 when the LDS image cannot hold the scene
 extern int g_bvh_ct;    // SAH node-visit cost in percent of a sphere test
 extern int g_lb_res;    // light-buffer cells per cube-map face edge: 0 = none, -1 = by scene size
+extern int g_csg_hier_min;  // boxed Csg units from which their hierarchy is built
 // render-time tuning copied into every scene at its creation (rt_scene::tune)
 extern std::mutex g_tune_mu;
 extern WfTuning g_tune_defaults;
@@ -349,7 +350,8 @@ int render_banded(rt_scene* s, std::unique_lock<std::mutex>& lk, rt_scene::HostC
                   uint32_t max_depth, uint32_t aa, double* out_rgb, bool host_ready = false);
 // the fast path can serve `s` (a hierarchy to cull with, not switched off)
 inline bool fast_path(const rt_scene* s) {
-  return s->tune.accel != 0 && (s->dev.n_bvh > 0 || s->dev.n_obvh > 0 || s->dev.n_lbvh > 0 || s->dev.n_tbvh > 0);
+  return s->tune.accel != 0 && (s->dev.n_bvh > 0 || s->dev.n_obvh > 0 || s->dev.n_lbvh > 0 || s->dev.n_tbvh > 0 ||
+                                 s->dev.n_ubvh > 0);
 }
 
 inline PpmHeader ppm_header(uint32_t w, uint32_t h) {  // image/ppm.rs:53-63

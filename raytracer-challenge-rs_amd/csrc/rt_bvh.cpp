@@ -729,6 +729,127 @@ std::vector<BvhNode> build_tri_bvh(std::vector<TriRec>& recs, int leaf_size, int
   return nodes;
 }
 
+// The padded world box of one Csg unit (DESIGN.md §5.2 "Csg units: the fifth hierarchy").
+// A leaf's roots lie on its own surface in its own space: the unit sphere, the cube
+// [-1, 1]^3, the cylinder's wall and caps inside [-1, 1] x [min, max] x [-1, 1]. That region
+// goes up the forward chain (the leaf's matrix, then each enclosing Csg's, innermost first),
+// one region_box per matrix, each with its own pad_axis and its own cond <= 1e6 rule; the
+// product of the chain's condition numbers, a bound on the condition of the product, must
+// stay below 1e6 too. The device sends the ray DOWN the chain, one rounded transform after
+// another: with X_j a bound on |o_j|_inf and |t d_j|_inf at level j and G_j = |F_1|_inf ..
+// |F_j|_inf, the world point o + t d is within sum_j 16 u X_j G_j of the exact image of the
+// leaf-space point (u = 2^-53; 3 products and 3 sums per component, for origin and
+// direction), which is added to every side, doubled, for rays from |o|_inf <= kUnitOriginMax
+// (|t d|_inf <= |o|_inf + |box|_inf, since the point lies in the box). A cube's region is
+// widened first for its parallel-axis rule (below).
+bool csg_unit_box(const CsgOp* ops, int first, int n, const CsgRec* nodes, const OtherRec* leaves, double lo[3],
+                  double hi[3]) {
+  const double* chain[kCsgMaxDepth + 1];
+  int lvl = 0;
+  Box all;
+  bool any = false;
+  for (int pc = first; pc < first + n; ++pc) {
+    const CsgOp& op = ops[pc];
+    if (op.code == kCsgEnter) {
+      if (lvl >= kCsgMaxDepth) return false;
+      chain[lvl++] = nodes[op.arg].m;
+      continue;
+    }
+    if (op.code == kCsgExit) {
+      if (--lvl < 0) return false;
+      continue;
+    }
+    if (op.code != kCsgLeaf) continue;  // a group's gate moves no ray
+    const OtherRec& r = leaves[op.arg];
+    // planes are unbounded; a cone's a ~ 0 branch pushes a root off the cone (other_box)
+    if (r.kind != 0 && r.kind != 2 && r.kind != 3) return false;
+    double L[3] = {-1.0, -1.0, -1.0}, U[3] = {1.0, 1.0, 1.0};
+    if (r.kind == 3) {  // open or closed: the walk culls over the line, so no closed-solid argument is needed
+      if (!std::isfinite(r.minimum) || !std::isfinite(r.maximum) || !(r.minimum <= r.maximum)) return false;
+      L[1] = r.minimum;
+      U[1] = r.maximum;
+    }
+    // the matrices in the order the ray meets them: the outermost Csg's first, the leaf's last
+    const double* mats[kCsgMaxDepth + 1];
+    for (int j = 0; j < lvl; ++j) mats[j] = chain[j];
+    mats[lvl] = r.m;
+    double na[kCsgMaxDepth + 1], nf[kCsgMaxDepth + 1], K = 1.0;
+    for (int j = 0; j <= lvl; ++j) {
+      double F[3][3];
+      const double cond = invert3(mats[j], F);
+      if (!(cond <= 1e6)) return false;
+      K *= cond;
+      na[j] = nf[j] = 0.0;
+      for (int i = 0; i < 3; ++i) {
+        na[j] = std::max(na[j], std::fabs(mats[j][4 * i]) + std::fabs(mats[j][4 * i + 1]) + std::fabs(mats[j][4 * i + 2]));
+        nf[j] = std::max(nf[j], std::fabs(F[i][0]) + std::fabs(F[i][1]) + std::fabs(F[i][2]));
+      }
+    }
+    if (!(K <= 1e6)) return false;
+    // the leaf's region (a sphere's exact extent) under its own matrix, then up the chain
+    auto chain_box = [&](const double* lo3, const double* hi3, Box& out) {
+      if (!region_box(r, lo3, hi3, out.lo, out.hi)) return false;
+      for (int j = lvl - 1; j >= 0; --j) {
+        OtherRec q{};
+        q.kind = 2;
+        for (int e = 0; e < 12; ++e) q.m[e] = mats[j][e];
+        Box up;
+        if (!region_box(q, out.lo, out.hi, up.lo, up.hi)) return false;
+        out = up;
+      }
+      return true;
+    };
+    auto max_abs = [](const Box& x) {
+      double m = 0.0;
+      for (int a = 0; a < 3; ++a) m = std::max(m, std::max(std::fabs(x.lo[a]), std::fabs(x.hi[a])));
+      return m;
+    };
+    Box b;
+    if (!chain_box(L, U, b)) return false;
+    double bw = max_abs(b);
+    if (r.kind == 2) {
+      // Cube::check_axis (cube.rs:30-47) takes an axis with |d| < EPSILON for parallel: the roots
+      // come from the other axes, and on that one the point is o + t d with |o| <= 1, up to
+      // |t| EPSILON outside the slab. With |d|_inf >= kUnitDirMin and the point p = o + t d,
+      // |t| <= (|o|_inf + |p|_inf) / kUnitDirMin, and |p|_inf <= (1 + e) bw for the cube widened
+      // by e: e = EPSILON (Omax + bw) / dmin / (1 - EPSILON bw / dmin) closes the bound.
+      const double q = kEpsilon * bw / kUnitDirMin;
+      if (!(q < 0.5)) return false;
+      const double e = kEpsilon * (kUnitOriginMax + bw) / kUnitDirMin / (1.0 - q) * (1.0 + 1e-9);
+      for (int a = 0; a < 3; ++a) { L[a] = -1.0 - e; U[a] = 1.0 + e; }
+      if (!chain_box(L, U, b)) return false;
+      bw = max_abs(b);
+    }
+    double X = 2.0 * kUnitOriginMax + bw, G = 1.0, err = 0.0;
+    for (int j = 0; j <= lvl; ++j) {
+      const double tr = std::max(std::fabs(mats[j][3]), std::max(std::fabs(mats[j][7]), std::fabs(mats[j][11])));
+      X = na[j] * X + tr;
+      G *= nf[j];
+      err += 16.0 * 0x1p-53 * X * G;
+    }
+    err *= 2.0;
+    if (!std::isfinite(err)) return false;
+    for (int a = 0; a < 3; ++a) {
+      b.lo[a] -= err;
+      b.hi[a] += err;
+      if (!std::isfinite(b.lo[a]) || !std::isfinite(b.hi[a])) return false;
+    }
+    all.grow(b);
+    any = true;
+  }
+  if (!any || lvl != 0) return false;
+  for (int a = 0; a < 3; ++a) { lo[a] = all.lo[a]; hi[a] = all.hi[a]; }
+  return true;
+}
+
+std::vector<BvhNode> build_unit_bvh(const std::vector<double>& boxes, int leaf_size, int* depth,
+                                    std::vector<int>* order, double trav_cost) {
+  std::vector<Box> bx(boxes.size() / 6);
+  for (size_t i = 0; i < bx.size(); ++i)
+    for (int a = 0; a < 3; ++a) { bx[i].lo[a] = boxes[6 * i + a]; bx[i].hi[a] = boxes[6 * i + 3 + a]; }
+  return build_over_boxes(bx, leaf_size, trav_cost, depth, order);
+}
+
 // ------------------------------------------------------------ light buffer
 // See rt_layout.hpp (LbCell) and DESIGN.md "Light buffer" for the argument.
 // Margins: the query (binary32, from the binary64 shadow-ray vector) lands

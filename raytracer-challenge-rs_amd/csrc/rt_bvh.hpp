@@ -3,6 +3,7 @@
 #include <stddef.h>
 #include <vector>
 
+#include "rt_csg.hpp"
 #include "rt_layout.hpp"
 
 namespace rtamd {
@@ -70,6 +71,22 @@ std::vector<BvhNode> build_line_bvh(std::vector<QuadRec>& recs, std::vector<Cone
 bool tri_box(const TriRec& r, double lo[3], double hi[3]);
 std::vector<BvhNode> build_tri_bvh(std::vector<TriRec>& recs, int leaf_size, int* depth = nullptr,
                                    double trav_cost = 1.0);
+
+// The Csg units' hierarchy (rt_trace.hpp unit_trace, DESIGN.md §5.2 "Csg units: the fifth
+// hierarchy"). csg_unit_box: the padded world box of one unit's program ops[first .. first + n).
+// For every ray (o, d) with |o|_inf <= kUnitOriginMax and every leaf of the unit, each root t
+// the leaf's test produces on the chained ray (the world ray through every enclosing Csg's
+// inverse one after another, then the leaf's) has o + t d inside the box: a superset of what
+// survives the filters. The box comes from the leaves' own regions carried up the forward
+// chain; the reference's get_bounds() gate stays in the program and takes no part. False (the
+// unit stays in the exhaustive loop): a plane or cone leaf, a cylinder without finite bounds,
+// an ill-conditioned matrix or chain, a non-finite result.
+// build_unit_bvh: the hierarchy over such boxes (six doubles a unit: lo, hi); `order` receives
+// the units' leaf order. Empty when there are none.
+bool csg_unit_box(const CsgOp* ops, int first, int n, const CsgRec* nodes, const OtherRec* leaves, double lo[3],
+                  double hi[3]);
+std::vector<BvhNode> build_unit_bvh(const std::vector<double>& boxes, int leaf_size, int* depth,
+                                    std::vector<int>* order, double trav_cost = 1.0);
 
 // Light buffer over the shadow-casting records, one cube map of R x R cells
 // per face per light (rt_layout.hpp LbCell; DESIGN.md "Light buffer").

@@ -425,67 +425,77 @@ __device__ __forceinline__ void csg_fold(const DevScene& sc, const CsgList& xs, 
     h.t = bt; h.key = bk; h.hin = n_neg & 1;
   }
 }
-// World::intersect's share of the Csg units (world.rs:31-38 over the Csgs of
-// World::objects, and over those inside groups, whose gates come first).
-// Per unit: the ray goes down the chain one matrix after another (never a
+// World::intersect's share of one Csg unit (world.rs:31-38 over the Csgs of
+// World::objects, and over those inside groups, whose gates the caller tests first).
+// The ray goes down the chain one matrix after another (never a
 // product), every gate is the reference's, in binary64; the leaves append to
 // one list, each Csg node closes its tail (rt_csg.hpp), the root's survivors
 // fold into `h`. COUNT_ONLY: the gates alone, for a counted launch's ray that
-// was answered before (count_rest_gates). Inlined like every other trace
+// was answered before (count_rest_gates) or whose walk never reached the unit
+// (count_hier_gates). Inlined like every other trace
 // function: the list, the ray stack and the list starts are private arrays
 // indexed per lane (scratch, as the walks' stacks), and nothing is reached
 // through a pointer to a local.
 template <bool SHADOW, bool COUNT_ONLY>
-__device__ __forceinline__ void csg_units(const DevScene& sc, V3 o, V3 d, Hit& h, unsigned& n_disc, GateSkips* skips) {
+__device__ __forceinline__ void csg_unit_eval(const DevScene& sc, const CsgUnit un, V3 o, V3 d, Hit& h, unsigned& disc,
+                                              GateSkips& sk) {
+  CsgList xs;
+  xs.n = 0;
+  double ray[kCsgMaxDepth + 1][6];
+  int start[kCsgMaxDepth + 1];
+  int lvl = 0;
+  V3 co = o, cd = d;
+  const int end = un.first + un.n;
+  for (int pc = un.first; pc < end;) {
+    const CsgOp op = sc.csg_ops[pc];
+    if (op.code == kCsgEnter) {
+      const CsgRec* c = sc.csg_nodes + op.arg;
+      const V3 lo = m34_point(c->m, co);  // Ray::transform by the Csg's own inverse (ray.rs:26-28)
+      const V3 ld = v3(c->m[0] * cd.x + c->m[1] * cd.y + c->m[2] * cd.z, c->m[4] * cd.x + c->m[5] * cd.y + c->m[6] * cd.z,
+                       c->m[8] * cd.x + c->m[9] * cd.y + c->m[10] * cd.z);
+      if (lvl >= kCsgMaxDepth || !bbox_intersects(c->lo, c->hi, lo, ld)) {  // csg.rs:116-118
+        csg_skip(sk, op.counts);
+        pc = op.skip_to;
+        continue;
+      }
+      ray[lvl][0] = co.x; ray[lvl][1] = co.y; ray[lvl][2] = co.z;
+      ray[lvl][3] = cd.x; ray[lvl][4] = cd.y; ray[lvl][5] = cd.z;
+      start[lvl] = xs.n;
+      ++lvl;
+      co = lo; cd = ld;
+    } else if (op.code == kCsgExit) {
+      --lvl;
+      if (!COUNT_ONLY) csg_close(xs, start[lvl], sc.csg_nodes[op.arg].op, sc.csg_nodes[op.arg].split);
+      co = v3(ray[lvl][0], ray[lvl][1], ray[lvl][2]);
+      cd = v3(ray[lvl][3], ray[lvl][4], ray[lvl][5]);
+    } else if (op.code == kCsgGroup) {
+      if (!bbox_intersects((cGroupRec)sc.groups + op.arg, co, cd)) {  // group.rs:50-52, the ray it is handed
+        csg_skip(sk, op.counts);
+        pc = op.skip_to;
+        continue;
+      }
+    } else {
+      if (!COUNT_ONLY) csg_leaf(sc.csg_leaves + op.arg, co, cd, xs, disc);
+    }
+    ++pc;
+  }
+  if (!COUNT_ONLY) csg_fold<SHADOW>(sc, xs, h);
+}
+// The units `units[0 .. n)`, each behind the gate of the groups around it (Group::intersect,
+// group.rs:49-58): the exhaustive paths pass the scene's full list in the reference's order,
+// the fast path the units outside the hierarchy (trace_rest; unit_trace walks the others).
+template <bool SHADOW, bool COUNT_ONLY>
+__device__ __forceinline__ void csg_units(const DevScene& sc, const CsgUnit* units, int n, V3 o, V3 d, Hit& h,
+                                          unsigned& n_disc, GateSkips* skips) {
   GateSkips sk;
   unsigned disc = 0;
-  for (int u = 0; u < sc.n_csg_units; ++u) {
-    const CsgUnit un = sc.csg_units[u];
-    if (un.gate && !group_gate(sc, un.gate, o, d)) {  // Group::intersect (group.rs:49-58)
+  for (int u = 0; u < n; ++u) {
+    const CsgUnit un = units[u];
+    if (un.gate && !group_gate(sc, un.gate, o, d)) {
       csg_skip(sk, un.counts);
       continue;
     }
-    CsgList xs;
-    xs.n = 0;
-    double ray[kCsgMaxDepth + 1][6];
-    int start[kCsgMaxDepth + 1];
-    int lvl = 0;
-    V3 co = o, cd = d;
-    const int end = un.first + un.n;
-    for (int pc = un.first; pc < end;) {
-      const CsgOp op = sc.csg_ops[pc];
-      if (op.code == kCsgEnter) {
-        const CsgRec* c = sc.csg_nodes + op.arg;
-        const V3 lo = m34_point(c->m, co);  // Ray::transform by the Csg's own inverse (ray.rs:26-28)
-        const V3 ld = v3(c->m[0] * cd.x + c->m[1] * cd.y + c->m[2] * cd.z, c->m[4] * cd.x + c->m[5] * cd.y + c->m[6] * cd.z,
-                         c->m[8] * cd.x + c->m[9] * cd.y + c->m[10] * cd.z);
-        if (lvl >= kCsgMaxDepth || !bbox_intersects(c->lo, c->hi, lo, ld)) {  // csg.rs:116-118
-          csg_skip(sk, op.counts);
-          pc = op.skip_to;
-          continue;
-        }
-        ray[lvl][0] = co.x; ray[lvl][1] = co.y; ray[lvl][2] = co.z;
-        ray[lvl][3] = cd.x; ray[lvl][4] = cd.y; ray[lvl][5] = cd.z;
-        start[lvl] = xs.n;
-        ++lvl;
-        co = lo; cd = ld;
-      } else if (op.code == kCsgExit) {
-        --lvl;
-        if (!COUNT_ONLY) csg_close(xs, start[lvl], sc.csg_nodes[op.arg].op, sc.csg_nodes[op.arg].split);
-        co = v3(ray[lvl][0], ray[lvl][1], ray[lvl][2]);
-        cd = v3(ray[lvl][3], ray[lvl][4], ray[lvl][5]);
-      } else if (op.code == kCsgGroup) {
-        if (!bbox_intersects((cGroupRec)sc.groups + op.arg, co, cd)) {  // group.rs:50-52, the ray it is handed
-          csg_skip(sk, op.counts);
-          pc = op.skip_to;
-          continue;
-        }
-      } else {
-        if (!COUNT_ONLY) csg_leaf(sc.csg_leaves + op.arg, co, cd, xs, disc);
-      }
-      ++pc;
-    }
-    if (!COUNT_ONLY) csg_fold<SHADOW>(sc, xs, h);
+    csg_unit_eval<SHADOW, COUNT_ONLY>(sc, un, o, d, h, disc, sk);
   }
   n_disc += disc;
   if (skips) { skips->sph += sk.sph; skips->plane += sk.plane; skips->other += sk.other; }
@@ -498,7 +508,8 @@ __device__ __forceinline__ void csg_units(const DevScene& sc, V3 o, V3 d, Hit& h
 // FAST: the fast path's remainder (the records outside both hierarchies;
 // the other bounded records are traversed by other_trace).
 // TRIS: the triangles too (the kernels of scenes without solids never meet one).
-// CSG: the Csg units too (csg_units; the same records on both paths).
+// CSG: the Csg units too (csg_units): every unit, or on the fast path those outside the
+// units' hierarchy (fx_units; unit_trace walks the others).
 template <bool SHADOW, bool QUADS = true, bool FAST = false, bool TRIS = QUADS, bool CSG = false>
 __device__ __forceinline__ void trace_rest(const DevScene& sc, V3 o, V3 d, Hit& h, unsigned& n_disc,
                                            GateSkips* skips = nullptr) {
@@ -549,7 +560,9 @@ __device__ __forceinline__ void trace_rest(const DevScene& sc, V3 o, V3 d, Hit& 
       tri_test<SHADOW>(tr + j, o, d, h);
     }
   }
-  if constexpr (CSG) csg_units<SHADOW, false>(sc, o, d, h, n_disc, skips);
+  if constexpr (CSG)
+    csg_units<SHADOW, false>(sc, FAST ? sc.fx_units : sc.csg_units, FAST ? sc.n_fx_units : sc.n_csg_units, o, d, h, n_disc,
+                             skips);
 }
 
 // The group gates trace_rest<.., QUADS, true> meets, without its tests: a counted
@@ -562,7 +575,7 @@ __device__ __forceinline__ void count_rest_gates(const DevScene& sc, V3 o, V3 d,
     Hit none;
     hit_init(none);
     unsigned nd = 0;
-    csg_units<true, true>(sc, o, d, none, nd, &sk);
+    csg_units<true, true>(sc, sc.fx_units, sc.n_fx_units, o, d, none, nd, &sk);
   }
   cSphereGen sg = (cSphereGen)sc.fx_gen;
   for (int j = 0; j < sc.n_fx_gen; ++j)

@@ -122,6 +122,11 @@ struct alignas(16) CsgUnit {
   int32_t first, n, gate, counts;
 };
 static_assert(sizeof(QuadRec) == 128, "QuadRec must stay 128 B");
+// The rays the unit hierarchy's padding is sized for (rt_bvh.cpp csg_unit_box, rt_trace.hpp
+// unit_trace): finite, |d|_inf at least kUnitDirMin (a unit vector's is 0.577), from origins
+// with |o|_inf at most kUnitOriginMax (a cube leaf's box grows with it: EPSILON times the
+// longest t such a ray can reach the cube with).
+constexpr double kUnitDirMin = 0.5, kUnitOriginMax = 4096.0;
 
 // Bounding-volume hierarchies (built on the host, rt_bvh.cpp): one over the
 // SphereDiag records, one over the other bounded records (OtherRec: general-
@@ -352,6 +357,13 @@ struct DevScene {
   const CsgRec* csg_nodes;
   const OtherRec* csg_leaves;
   int32_t n_csg_units, n_csg_sph, n_csg_planes, n_csg_other;
+  // on the fast path the hierarchy over the units' padded world boxes (unit_trace; `urec`: the
+  // boxed units' records in its leaf order) and the units it does not hold (`fx_units`, every
+  // one of them evaluated by trace_rest); programs, nodes and leaves stay where they are
+  const BvhNode* ubvh;  // nullptr when there is none
+  const CsgUnit* urec;
+  const CsgUnit* fx_units;
+  int32_t n_ubvh, n_urec, n_fx_units, ubvh_depth;
 };
 
 constexpr int32_t kOwnOutside = 0x40000000, kOwnIndex = 0x3FFFFFFF;  // DevScene::obj_diag

@@ -481,6 +481,39 @@ int rt_scene_create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int
     trec.clear();
     tbvh.clear();
   }
+  // ... and over the Csg units (unit_trace): only the 16-byte unit records are split and put in
+  // leaf order; a unit without a box (a plane or cone leaf, an unbounded cylinder, an
+  // ill-conditioned chain) stays in the loop. Built from g_csg_hier_min boxed units on, with no
+  // "only hierarchy" exception: a handful of units is cheaper behind the reference's own gates.
+  std::vector<CsgUnit> urec, fx_units;
+  std::vector<double> unit_boxes;
+  for (const CsgUnit& u : csg_units) {
+    if (csg_unit_box(csg_ops.data(), u.first, u.n, csg_nodes.data(), csg_leaves.data(), blo, bhi)) {
+      urec.push_back(u);
+      unit_boxes.insert(unit_boxes.end(), blo, blo + 3);
+      unit_boxes.insert(unit_boxes.end(), bhi, bhi + 3);
+    } else {
+      fx_units.push_back(u);
+    }
+  }
+  int ubvh_depth = 0;
+  std::vector<BvhNode> ubvh;
+  if (!urec.empty() && urec.size() >= (size_t)g_csg_hier_min) {
+    // (a unit's evaluation costs tens of node visits: one unit a leaf unless the knob says otherwise)
+    std::vector<int> order;
+    ubvh = build_unit_bvh(unit_boxes, g_bvh_leaf > 0 ? g_bvh_leaf : 1, &ubvh_depth, &order, 0.05);
+    if (!ubvh.empty()) {
+      std::vector<CsgUnit> in_order;
+      for (int i : order) in_order.push_back(urec[(size_t)i]);
+      urec.swap(in_order);
+    }
+  }
+  if (ubvh.empty() || ubvh_depth > kBvhMaxDepth) {  // none, or deeper than unit_trace's stack: the loop
+    fx_units = csg_units;
+    urec.clear();
+    ubvh.clear();
+    ubvh_depth = 0;
+  }
   std::vector<int32_t> lrec_clus(line_rec.size(), -1);  // each cone's cluster (line_trace's pre-pass check)
   for (size_t c = 0; c < lclus.size(); ++c)
     for (int32_t j = lclus[c].first; j < lclus[c].first + lclus[c].count; ++j) lrec_clus[(size_t)lcone[(size_t)j]] = (int32_t)c;
@@ -545,7 +578,10 @@ int rt_scene_create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int
   const size_t o_co = align(o_cu + (csg_units.size() + 1) * sizeof(CsgUnit));
   const size_t o_cn = align(o_co + (csg_ops.size() + 1) * sizeof(CsgOp));
   const size_t o_cl = align(o_cn + (csg_nodes.size() + 1) * sizeof(CsgRec));
-  const size_t total = align(o_cl + (csg_leaves.size() + 1) * sizeof(OtherRec)) + 256;
+  const size_t o_ub = align(o_cl + (csg_leaves.size() + 1) * sizeof(OtherRec));
+  const size_t o_ur = align(o_ub + (ubvh.size() + 1) * sizeof(BvhNode));
+  const size_t o_ux = align(o_ur + (urec.size() + 1) * sizeof(CsgUnit));
+  const size_t total = align(o_ux + (fx_units.size() + 1) * sizeof(CsgUnit)) + 256;
   std::vector<unsigned char> host(total, 0);
   if (!diag.empty()) std::memcpy(&host[o_diag], diag.data(), diag.size() * sizeof(SphereDiag));
   if (!gen.empty()) std::memcpy(&host[o_gen], gen.data(), gen.size() * sizeof(SphereGen));
@@ -598,6 +634,9 @@ int rt_scene_create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int
   if (!csg_ops.empty()) std::memcpy(&host[o_co], csg_ops.data(), csg_ops.size() * sizeof(CsgOp));
   if (!csg_nodes.empty()) std::memcpy(&host[o_cn], csg_nodes.data(), csg_nodes.size() * sizeof(CsgRec));
   if (!csg_leaves.empty()) std::memcpy(&host[o_cl], csg_leaves.data(), csg_leaves.size() * sizeof(OtherRec));
+  if (!ubvh.empty()) std::memcpy(&host[o_ub], ubvh.data(), ubvh.size() * sizeof(BvhNode));
+  if (!urec.empty()) std::memcpy(&host[o_ur], urec.data(), urec.size() * sizeof(CsgUnit));
+  if (!fx_units.empty()) std::memcpy(&host[o_ux], fx_units.data(), fx_units.size() * sizeof(CsgUnit));
   if (!lb.cells.empty()) {
     std::memcpy(&host[o_lc], lb.cells.data(), lb.cells.size() * sizeof(LbCell));
     if (!lb.ov.empty()) std::memcpy(&host[o_lv], lb.ov.data(), lb.ov.size() * sizeof(uint16_t));
@@ -691,6 +730,13 @@ int rt_scene_create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int
   s->dev.n_csg_sph = n_csg_kind[0];
   s->dev.n_csg_planes = n_csg_kind[1];
   s->dev.n_csg_other = n_csg_kind[2];
+  s->dev.ubvh = ubvh.empty() ? nullptr : (const BvhNode*)(b + o_ub);
+  s->dev.urec = (const CsgUnit*)(b + o_ur);
+  s->dev.fx_units = (const CsgUnit*)(b + o_ux);
+  s->dev.n_ubvh = (int32_t)ubvh.size();
+  s->dev.n_urec = (int32_t)urec.size();
+  s->dev.n_fx_units = (int32_t)fx_units.size();
+  s->dev.ubvh_depth = ubvh_depth;
   s->dev.n_diag = (int32_t)diag.size();
   s->dev.n_gen = (int32_t)gen.size();
   s->dev.n_planes = (int32_t)planes.size();

@@ -795,14 +795,105 @@ __device__ __forceinline__ void tri_trace(const DevScene& sc, V3 o, V3 d, double
     e = nn > 0 ? next[0] : (sp > 0 ? stk[--sp] : kBvhEmpty);
   }
 }
+// The Csg units' hierarchy (DESIGN.md §5.2 "Csg units: the fifth hierarchy"): binary nodes over
+// the units' padded world boxes (rt_bvh.cpp csg_unit_box: every root any leaf of the unit
+// produces on the chained ray lies in the box, filtered away or not). A unit is no closed convex
+// solid: after the filters a leaf can keep an odd number of roots behind the origin, and it is
+// then a `containers` entry (csg_fold) although the ray's [0, t_hi] never meets the box. The
+// line hierarchy's rule therefore: a child is entered when its box meets the ray's line
+// within (-inf, t_hi] (radiance rays) or [0, distance) (shadow rays: only those roots block).
+// A unit whose box the line misses adds nothing to its list, so nothing to `h`. At a leaf each
+// unit is evaluated behind the gate of the groups around it, as csg_units does; the gates'
+// skips are not counted here (a counted launch owes them for the units the walk never reached
+// too: count_hier_gates). The visiting order cannot change the answer: better(t, key) is a
+// total order, and push_container keeps the top two by (t, key) whatever order it is fed in,
+// as the other walks feed it in theirs. The boxes' padding covers finite rays with |d|_inf >=
+// kUnitDirMin from origins with |o|_inf <= kUnitOriginMax (every ray the pipeline makes itself
+// is a unit vector); any other ray (a caller's, a NaN) evaluates every unit of the hierarchy.
+template <bool SHADOW>
+__device__ __forceinline__ void unit_trace(const DevScene& sc, V3 o, V3 d, double t_shadow, Hit& h, unsigned& n_disc,
+                                           unsigned& n_tests, unsigned& n_boxes) {
+  if (sc.n_ubvh == 0 || (SHADOW && h.key >= 0 && h.t < t_shadow)) return;
+  const double dm = fmax(fmax(fabs(d.x), fabs(d.y)), fabs(d.z)), om = fmax(fmax(fabs(o.x), fabs(o.y)), fabs(o.z));
+  const bool walk = dm < INFINITY && dm >= kUnitDirMin && om <= kUnitOriginMax && d.x == d.x && d.y == d.y &&
+                    d.z == d.z && o.x == o.x && o.y == o.y && o.z == o.z;
+  const BvhNode* nodes = sc.ubvh;
+  float M[3];
+  root_bound(nodes, M);
+  const SlabRay sr = slab_ray(o, d, M);
+  const float t_lo = SHADOW ? 0.0f : -INFINITY;
+  float t_hi = f32_up(SHADOW ? t_shadow : h.t);
+  GateSkips none;
+  unsigned disc = 0;
+  // One evaluation site (the unit's list and ray stack are about 1 KB of scratch a copy): the
+  // pending leaf's units [first, first + cnt), then the walk to the next leaf whose box the line
+  // meets; without the walk the whole record array is the one leaf. The stack holds child codes,
+  // nodes and leaves alike, the near child on top: at most one waiting per level and two at the last.
+  int stk[kBvhMaxDepth + 4];
+  int sp = 0;
+  if (walk) stk[sp++] = 0;
+  int first = 0, cnt = walk ? 0 : sc.n_urec;
+  while (true) {
+    for (int k = first; k < first + cnt; ++k) {
+      const CsgUnit un = sc.urec[k];
+      ++n_tests;
+      if (un.gate && !group_gate(sc, un.gate, o, d)) continue;  // Group::intersect (group.rs:49-58)
+      csg_unit_eval<SHADOW, false>(sc, un, o, d, h, disc, none);
+      if constexpr (SHADOW) {
+        if (h.key >= 0 && h.t < t_shadow) { n_disc += disc; return; }  // shadowed: done
+      } else {
+        t_hi = f32_up(h.t);
+      }
+    }
+    cnt = 0;
+    while (sp > 0) {
+      const int e = stk[--sp];
+      if (e < 0) {  // a leaf
+        const int lc = -(e + 1);
+        first = lc >> 7;
+        cnt = lc & 127;
+        break;
+      }
+      const BvhNode& nd = nodes[e];
+      int next[2], nn = 0;
+      float tin[2] = {0.0f, 0.0f};
+      for (int c = 0; c < 2; ++c) {
+        const int32_t code = nd.child[c];
+        if (code == kBvhEmpty) continue;
+        ++n_boxes;
+        float t_in;
+        if (!slab_hit32(nd.lo[c], nd.hi[c], sr, t_hi, t_in, t_lo)) continue;
+        tin[nn] = t_in;
+        next[nn++] = code;
+      }
+      if (nn == 2) {
+        const bool flip = tin[1] < tin[0];
+        stk[sp++] = flip ? next[0] : next[1];
+        stk[sp++] = flip ? next[1] : next[0];
+      } else if (nn == 1) {
+        stk[sp++] = next[0];
+      }
+    }
+    if (cnt == 0) break;
+  }
+  n_disc += disc;
+}
 // Counted launches (the reference's shape tests come from the group gates
 // each ray met, GateSkips): the gates of the grouped records the other
 // records' and the triangles' hierarchies hold (trace_rest counts those of the
 // records it loops over; the line hierarchy holds no grouped record). Every
 // record is visited here, so only counted launches call it.
-template <bool TRIS>
+// CSG: the gates inside and around the units their hierarchy holds too, in one pass over all of
+// them (the walk counts none: it never reaches most units, and each owes its leaves all the same).
+template <bool TRIS, bool CSG = false>
 __device__ __forceinline__ void count_hier_gates(const DevScene& sc, V3 o, V3 d, GateSkips& sk) {
   if (!sc.n_groups) return;
+  if constexpr (CSG) {
+    Hit none;
+    hit_init(none);
+    unsigned nd = 0;
+    csg_units<true, true>(sc, sc.urec, sc.n_urec, o, d, none, nd, &sk);
+  }
   const cQuadRec orec = (cQuadRec)sc.orec;
   for (int k = 0; k < sc.n_orec; ++k) {
     const int g = orec[k].gate;
@@ -1106,7 +1197,7 @@ __device__ __forceinline__ void lb_walk(const DevScene& sc, SD sd, const float* 
 // gates of the records it did not get to (count_rest_gates; the caller counts
 // the other hierarchy's, count_hier_gates).
 // TRIS: the scene has triangles (trace_rest's loop over those outside the hierarchy, tri_trace).
-// CSG: the scene has Csg units (trace_rest's csg_units).
+// CSG: the scene has Csg units (trace_rest's csg_units over those outside their hierarchy, unit_trace).
 template <bool QUADS, bool TALLY = false, bool TRIS = false, bool CSG = false, typename Image>
 __device__ __forceinline__ bool shadow_trace(const DevScene& sc, unsigned use_lb, const Image& img, unsigned l,
                                              V3 o, V3 d, double dist, unsigned& n_disc, unsigned& n_tests,
@@ -1130,6 +1221,7 @@ __device__ __forceinline__ bool shadow_trace(const DevScene& sc, unsigned use_lb
     line_trace<true>(sc, o, d, dist, h, n_tests, n_boxes);
   }
   if constexpr (TRIS) tri_trace<true>(sc, o, d, dist, h, n_tests, n_boxes);
+  if constexpr (CSG) unit_trace<true>(sc, o, d, dist, h, n_disc, n_tests, n_boxes);
   if (!(h.key >= 0 && h.t < dist)) {
     if (use_lb) lb_walk(sc, img.sd, img.delta, img.delta16, l, o, d, dist, h, n_disc, n_tests, skip);
     else img.template walk<true>(sc, o, d, dist, h, n_disc, n_tests, n_boxes);

@@ -417,7 +417,8 @@ hipError_t Wavefront::render(const DevScene& sc, const WfJob& job, hipStream_t s
   // reference's every-shape loop is asked for; counting never changes the algorithm
   const bool exhaustive = (flags & WF_EXHAUSTIVE) != 0;
   const bool count = (flags & WF_COUNT) != 0;
-  const bool bvh = tn.accel != 0 && !exhaustive && (sc.n_bvh > 0 || sc.n_obvh > 0 || sc.n_lbvh > 0 || sc.n_tbvh > 0);
+  const bool bvh = tn.accel != 0 && !exhaustive && (sc.n_bvh > 0 || sc.n_obvh > 0 || sc.n_lbvh > 0 || sc.n_tbvh > 0 ||
+                                                      sc.n_ubvh > 0);
   const bool fused = bvh;
   // (a counted render of a scene with groups traces every shadow ray: the reference's shape
   // tests then come from the group gates each ray met, GateSkips)

@@ -383,7 +383,7 @@ __device__ __forceinline__ void wf_trace_lds(const DevScene& sc, const WfLds& lv
       tri_test<SHADOW>(tr + j, o, d, h);
     }
   }
-  if constexpr (CSG) csg_units<SHADOW, false>(sc, o, d, h, n_disc, &sk);
+  if constexpr (CSG) csg_units<SHADOW, false>(sc, sc.csg_units, sc.n_csg_units, o, d, h, n_disc, &sk);
   hit_finish(h);
 }
 
@@ -739,7 +739,7 @@ __device__ __forceinline__ void shade_fused(const DevScene& sc, const DevCamera&
       const bool shadowed = shadow_trace<QUADS, TALLY, TRIS, CSG>(
           sc, a.use_lb, img, l, c.over, sdir, dist, t.sh_disc, t.sh_tests, t.sh_boxes, &t.gsk, own_first,
           own_out >= 0 && vdot(sdir, c.normal) >= 0.0 ? own_out : -1);
-      if (QUADS && a.count) count_hier_gates<TRIS>(sc, c.over, sdir, t.gsk);
+      if (QUADS && a.count) count_hier_gates<TRIS, CSG>(sc, c.over, sdir, t.gsk);
       ++t.sh_rays;
       term = lighting(*m, Lr, c.over, c.eyev, c.normal, shadowed, sdir);
     }
@@ -831,7 +831,7 @@ __global__ __launch_bounds__(kTraceBlock, 4) void wf_trace_fused(DevScene sc, De
     hit_init(h);
     if (valid) {
       wf_ray<CAM>(a, cam, slot, o, d);
-      if constexpr (TALLY && QUADS) count_hier_gates<TRIS>(sc, o, d, t.gsk);
+      if constexpr (TALLY && QUADS) count_hier_gates<TRIS, CSG>(sc, o, d, t.gsk);
       if constexpr (!Image::kPerLane) {
         // the chunk's frame (chunks never mix frames): its shared-origin primary records
         const unsigned pf = a.n_frames > 1 ? (c * 64u) / a.frame_rays : 0u;
@@ -845,6 +845,7 @@ __global__ __launch_bounds__(kTraceBlock, 4) void wf_trace_fused(DevScene sc, De
         line_trace<false>(sc, o, d, 0.0, h, t.tests, t.boxes);
       }
       if constexpr (TRIS) tri_trace<false>(sc, o, d, 0.0, h, t.tests, t.boxes);
+      if constexpr (CSG) unit_trace<false>(sc, o, d, 0.0, h, t.disc, t.tests, t.boxes);
       if constexpr (Image::kPerLane) img.template walk<false>(sc, o, d, 0.0, h, t.disc, t.tests, t.boxes);
     }
     hit_finish(h);
