@@ -580,19 +580,44 @@ bool other_box(const OtherRec& r, double lo[3], double hi[3]) {
   if (r.kind != 0 && r.kind != 2 && r.kind != 3) return false;
   double L[3] = {-1.0, -1.0, -1.0}, U[3] = {1.0, 1.0, 1.0};
   if (r.kind == 3) {  // cylinder: culled here only when closed, with finite caps' planes
-    // An OPEN tube goes to the line hierarchy: the culling argument here needs
-    // "an odd number of t < 0 roots => the origin lies inside the box"
-    // (DESIGN.md §5.2), true for closed convex solids only. A backward line can
-    // cross one wall of an open tube within [min, max] and leave through the
-    // open end, so the tube is a `containers` entry (intersection.rs:63-90) for
-    // a ray whose [0, t_hi] never meets its box.
+    // An OPEN tube goes to the line hierarchy: the culling argument of spheres and
+    // cubes needs "an odd number of t < 0 roots => the origin lies inside the box"
+    // (DESIGN.md §5.2). A backward line can cross one wall of an open tube within
+    // [min, max] and leave through the open end, so the tube is a `containers`
+    // entry (intersection.rs:63-90) for a ray whose [0, t_hi] never meets its box.
+    // A CLOSED cylinder breaks that rule too: with dx^2 + dz^2 < EPSILON
+    // (cylinder.rs:88-92) only the caps are tested, and the line can cross one cap
+    // inside the disc and leave through the wall without a root. Its box holds
+    // every root all the same (a cap root lies on the cap's disc, a wall root on
+    // the wall between the caps), so it stays here and is culled by the line
+    // hierarchy's rule: other_needs_line, build_other_bvh, other_trace.
     if (!r.closed) return false;
     if (!std::isfinite(r.minimum) || !std::isfinite(r.maximum) || !(r.minimum <= r.maximum)) return false;
     L[1] = r.minimum;
     U[1] = r.maximum;
   }
-  return region_box(r, L, U, lo, hi);
+  if (!region_box(r, L, U, lo, hi)) return false;
+  if (r.kind == 2) {
+    // Cube::check_axis (cube.rs:30-47) takes an axis with |d| < EPSILON for parallel: the roots
+    // come from the other axes, and on that one the point is o + t d with |o| <= 1, up to
+    // |t| EPSILON outside the slab. For rays with |d|_inf >= kOtherDirMin from |o|_inf <=
+    // kOtherOriginMax (from farther off other_trace grows every box for the ray, other_far_pad;
+    // shorter rays do not walk) and the point p = o + t d, |t| <= (|o|_inf + |p|_inf) /
+    // kOtherDirMin, and |p|_inf <= (1 + e) bw for the cube widened by e (bw: the largest
+    // coordinate of the unwidened box): e = EPSILON (Omax + bw) / dmin / (1 - EPSILON bw / dmin)
+    // closes the bound, as for a Csg unit's cube leaf (csg_unit_box).
+    double bw = 0.0;
+    for (int a = 0; a < 3; ++a) bw = std::max(bw, std::max(std::fabs(lo[a]), std::fabs(hi[a])));
+    const double q = kEpsilon * bw / kOtherDirMin;
+    if (!(q < 0.5)) return false;
+    const double e = kEpsilon * (kOtherOriginMax + bw) / kOtherDirMin / (1.0 - q) * (1.0 + 1e-9);
+    for (int a = 0; a < 3; ++a) { L[a] = -1.0 - e; U[a] = 1.0 + e; }
+    return region_box(r, L, U, lo, hi);
+  }
+  return true;
 }
+
+bool other_needs_line(const OtherRec& r) { return r.kind == 3; }
 
 bool line_box(const QuadRec& r, double lo[3], double hi[3]) {
   if (!(r.kind == 4 || (r.kind == 3 && !r.closed))) return false;
@@ -609,7 +634,24 @@ std::vector<BvhNode> build_other_bvh(std::vector<OtherRec>& recs, int leaf_size,
     if (!other_box(recs[i], boxes[i].lo, boxes[i].hi)) return {};  // the caller passes bounded records only
   std::vector<int> order;
   std::vector<BvhNode> nodes = build_over_boxes(boxes, leaf_size, trav_cost, depth, &order);
-  if (!nodes.empty()) apply_order(recs, order);
+  if (nodes.empty()) return nodes;
+  apply_order(recs, order);
+  // BvhNode::line: which children hold a record of the line rule
+  auto mark = [&](auto&& self, int32_t code) -> bool {
+    if (code == kBvhEmpty) return false;
+    if (code < 0) {
+      const int lc = -(code + 1), first = lc >> 7, cnt = lc & 127;
+      bool line = false;
+      for (int k = first; k < first + cnt; ++k) line = line || other_needs_line(recs[(size_t)k]);
+      return line;
+    }
+    BvhNode& nd = nodes[(size_t)code];
+    nd.line = 0;
+    for (int c = 0; c < 2; ++c)
+      if (self(self, nd.child[c])) nd.line |= 1u << c;
+    return nd.line != 0;
+  };
+  mark(mark, 0);
   return nodes;
 }
 

@@ -44,11 +44,23 @@ uint16_t f16_bits_up(double x);
 // The other bounded records (general-transform spheres, cubes, closed
 // cylinders with finite caps; rt_layout.hpp OtherRec): other_box gives the
 // padded world box of one (false for a cone, an open or unbounded cylinder,
-// an ill-conditioned transform: the line hierarchy or the exhaustive loop
-// takes those). build_other_bvh builds
-// the hierarchy over records that all have one (reordered in place into leaf
-// order); empty when there are none.
+// min > max or NaN bounds, a transform of condition above 1e6 or with a
+// non-finite entry, a cube too large for its widening: the line hierarchy or
+// the exhaustive loop takes those). The contract (tests/cpp/other_box_check.cpp):
+// for every finite ray with |d|_inf >= kOtherDirMin from |o|_inf <=
+// kOtherOriginMax, each finite root t the record's test produces has o + t d
+// inside the box (a cube's box is widened for Cube::check_axis's parallel
+// rule, which is what needs the ray domain; from a farther origin inside the
+// box grown by other_far_pad, rt_layout.hpp). For a sphere or a cube an odd
+// number of roots at t < 0 means the origin is inside the box, so those are
+// culled over [0, t_hi]; a closed cylinder (other_needs_line) keeps no such
+// rule (only its caps are tested when dx^2 + dz^2 < EPSILON) and is culled
+// over (-inf, t_hi] by radiance rays. build_other_bvh builds the hierarchy
+// over records that all have a box (reordered in place into leaf order) and
+// sets BvhNode::line for the children that hold a record of the line rule;
+// empty when there are none.
 bool other_box(const OtherRec& r, double lo[3], double hi[3]);
+bool other_needs_line(const OtherRec& r);
 std::vector<BvhNode> build_other_bvh(std::vector<OtherRec>& recs, int leaf_size, int* depth = nullptr,
                                      double trav_cost = 1.0);
 

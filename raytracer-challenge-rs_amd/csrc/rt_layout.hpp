@@ -127,6 +127,29 @@ static_assert(sizeof(QuadRec) == 128, "QuadRec must stay 128 B");
 // with |o|_inf at most kUnitOriginMax (a cube leaf's box grows with it: EPSILON times the
 // longest t such a ray can reach the cube with).
 constexpr double kUnitDirMin = 0.5, kUnitOriginMax = 4096.0;
+// The same for the hierarchy over the other bounded records (rt_bvh.cpp other_box, rt_trace.hpp
+// other_trace), whose cubes are widened by the same rule: e = EPSILON (kOtherOriginMax + |box|_inf)
+// / kOtherDirMin of the unit cube, every cube of every scene. Here the origin bound is 1024 (2 %,
+// against 8 % at the units' 4096), and a ray from farther off is not sent round every record (a
+// floor's horizon rows start their shadow and reflection rays there: two pixel rows of such
+// lanes, 800 tests each, nearly doubled the frame time of a divided group of 800,
+// profiles/other_box_ab.txt): it walks the hierarchy with every box grown by other_far_pad, which
+// is what a cube's root can add to its box from that origin. Rays that are not finite or have
+// |d|_inf < kOtherDirMin (only a caller's own) test every record.
+constexpr double kOtherDirMin = 0.5, kOtherOriginMax = 1024.0;
+// World-space growth per axis for a ray from |o|_inf = o_inf > kOtherOriginMax: a cube's root
+// leaves its slab by |t| EPSILON in object space, h |t| EPSILON on a world axis where the cube's
+// half extent is h <= m_axis (the hierarchy's largest coordinate on that axis, root_bound), and
+// |t| <= (o_inf + |p|_inf) / kOtherDirMin with |p|_inf <= m_max + the growth itself:
+// D = m_max EPSILON (o_inf + m_max) / dmin / (1 - m_max EPSILON / dmin) bounds every axis' growth,
+// so m_axis EPSILON (o_inf + m_max + D) / dmin bounds this one's. Negative: no bound (the caller
+// tests every record).
+constexpr double other_far_pad(double m_axis, double m_max, double o_inf) {
+  const double q = m_max * kEpsilon / kOtherDirMin;
+  if (!(q < 0.5) || !(o_inf < 1e300)) return -1.0;
+  const double D = m_max * kEpsilon * (o_inf + m_max) / kOtherDirMin / (1.0 - q);
+  return m_axis * kEpsilon * (o_inf + m_max + D) / kOtherDirMin * (1.0 + 1e-9);
+}
 
 // Bounding-volume hierarchies (built on the host, rt_bvh.cpp): one over the
 // SphereDiag records, one over the other bounded records (OtherRec: general-
@@ -136,12 +159,14 @@ constexpr double kUnitDirMin = 0.5, kUnitOriginMax = 4096.0;
 // OUTWARD from the padded binary64 boxes, so culling stays conservative
 // (DESIGN.md "Exact culling"). A child is an internal node index (>= 0), a
 // leaf code -(1 + (first << 7 | count)) over the (reordered) record array,
-// or kBvhEmpty.
+// or kBvhEmpty. `line` (the other records' hierarchy only, else 0): bit c set
+// when a record below child c must be culled over the ray's whole line
+// (rt_bvh.cpp other_box: the closed cylinders).
 struct alignas(64) BvhNode {
   float lo[2][3], hi[2][3];
   int32_t child[2];
   int32_t axis;
-  uint32_t pad;
+  uint32_t line;
 };
 static_assert(sizeof(BvhNode) == 64, "BvhNode must stay 64 B");
 // The same node in the pair layout the per-lane traversal reads

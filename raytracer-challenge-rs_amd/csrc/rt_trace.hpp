@@ -97,7 +97,8 @@ struct SlabRay {
 // (float)d rounds once (2^-24), v_rcp_f32 is within 1 ulp (2^-23); returned
 // widened to binary64 (exact), the value every plane constant is built from.
 __device__ __forceinline__ double slab_inv(double d) { return (double)__builtin_amdgcn_rcpf((float)d); }
-__device__ __forceinline__ SlabRay slab_ray(V3 o, V3 d, const float* M) {
+// `grow` (other_trace's far origins): every box taken as that much larger on each axis, in world units.
+__device__ __forceinline__ SlabRay slab_ray(V3 o, V3 d, const float* M, const double* grow = nullptr) {
   SlabRay r;
   const double oa[3] = {o.x, o.y, o.z}, da[3] = {d.x, d.y, d.z};
 #pragma unroll
@@ -105,7 +106,8 @@ __device__ __forceinline__ SlabRay slab_ray(V3 o, V3 d, const float* M) {
     if (fabs(da[a]) >= 0x1p-60 && fabs(oa[a]) <= 0x1p60 && M[a] <= 0x1p60f) {  // NaN fails
       const double inv = slab_inv(da[a]);
       const double oinv = oa[a] * inv;
-      const double delta = 0x1p-20 * fabs(inv) * ((double)M[a] + fabs(oa[a]));
+      double delta = 0x1p-20 * fabs(inv) * ((double)M[a] + fabs(oa[a]));
+      if (grow) delta = (delta + fabs(inv) * grow[a]) * (1.0 + 0x1p-20);
       const float on = (float)(oinv + delta), of = (float)(oinv - delta);
       r.inv[a] = (float)inv;
       r.c_lo[a] = inv >= 0.0 ? on : of;  // the lo plane is the entry plane when inv >= 0
@@ -598,30 +600,62 @@ __device__ __forceinline__ void stage_lds(uint4* dst, const uint4* src, int n) {
 // memory, private stack): the same culling rule and exactness argument as the
 // sphere hierarchy (DESIGN.md "Exact culling"). Scenes made of diagonal
 // spheres and planes (C3, C5) have no such hierarchy.
+// Two things go beyond that argument (rt_bvh.cpp other_box). A cube's box is widened for
+// Cube::check_axis's parallel rule, by a bound that holds for rays with |d|_inf >= kOtherDirMin
+// (every ray the pipeline makes itself is a unit vector) from origins with |o|_inf <=
+// kOtherOriginMax; from a farther origin every box is grown by other_far_pad for that ray
+// (slab_ray's `grow`), and a ray that is not finite, or shorter (only a caller's own), tests every
+// record of the hierarchy. And a closed cylinder can keep one root behind an origin outside its
+// box, so a child that holds one (BvhNode::line) is entered when its box meets the ray's line
+// within (-inf, t_hi] (radiance rays; shadow rays [0, distance): only those roots block), as the
+// line hierarchy does.
 template <bool SHADOW>
 __device__ __forceinline__ void other_trace(const DevScene& sc, V3 o, V3 d, double t_shadow, Hit& h,
                                             unsigned& n_disc, unsigned& n_tests, unsigned& n_boxes) {
   if (sc.n_obvh == 0 || (SHADOW && h.key >= 0 && h.t < t_shadow)) return;
+  const double dm = fmax(fmax(fabs(d.x), fabs(d.y)), fabs(d.z)), om = fmax(fmax(fabs(o.x), fabs(o.y)), fabs(o.z));
+  bool walk = dm < INFINITY && dm >= kOtherDirMin && om < INFINITY && d.x == d.x && d.y == d.y && d.z == d.z &&
+              o.x == o.x && o.y == o.y && o.z == o.z;
   const BvhNode* nodes = sc.obvh;
   float M[3];
   root_bound(nodes, M);
-  const SlabRay sr = slab_ray(o, d, M);
+  double grow[3] = {0.0, 0.0, 0.0};
+  const bool far = walk && om > kOtherOriginMax;
+  if (far) {
+    const double mm = fmax(fmax((double)M[0], (double)M[1]), (double)M[2]);
+    for (int a = 0; a < 3; ++a) {
+      grow[a] = other_far_pad((double)M[a], mm, om);
+      walk = walk && grow[a] >= 0.0;
+    }
+  }
+  const SlabRay sr = slab_ray(o, d, M, far ? grow : nullptr);
   float t_hi = f32_up(SHADOW ? t_shadow : h.t);
   int stk[kBvhMaxDepth + 4];
-  int sp = 0, e = 0;
+  // One test site, the leaf branch: without the walk the record array is handed to it in
+  // leaf codes of up to kBvhLeafMax records, `rest` being the first record not handed out yet.
+  int sp = 0, rest = walk ? sc.n_orec : 0;
+  auto pop = [&]() -> int {
+    if (sp > 0) return stk[--sp];
+    if (rest >= sc.n_orec) return kBvhEmpty;
+    const int cnt = min(kBvhLeafMax, sc.n_orec - rest), code = -(1 + ((rest << 7) | cnt));
+    rest += cnt;
+    return code;
+  };
+  int e = walk ? 0 : pop();
   while (e != kBvhEmpty) {
     if (e >= 0) {
       const BvhNode& nd = nodes[e];
+      const unsigned line = SHADOW ? 0u : nd.line;
       float t0 = 0.0f, t1 = 0.0f;
-      const bool h0 = slab_hit32(nd.lo[0], nd.hi[0], sr, t_hi, t0);
-      const bool h1 = nd.child[1] != kBvhEmpty && slab_hit32(nd.lo[1], nd.hi[1], sr, t_hi, t1);
+      const bool h0 = slab_hit32(nd.lo[0], nd.hi[0], sr, t_hi, t0, (line & 1u) ? -INFINITY : 0.0f);
+      const bool h1 = nd.child[1] != kBvhEmpty && slab_hit32(nd.lo[1], nd.hi[1], sr, t_hi, t1, (line & 2u) ? -INFINITY : 0.0f);
       n_boxes += 2;
       if (h0 && h1) {
         const bool flip = t1 < t0;
         stk[sp++] = flip ? nd.child[0] : nd.child[1];
         e = flip ? nd.child[1] : nd.child[0];
       } else {
-        e = h0 ? nd.child[0] : h1 ? nd.child[1] : (sp > 0 ? stk[--sp] : kBvhEmpty);
+        e = h0 ? nd.child[0] : h1 ? nd.child[1] : pop();
       }
     } else {
       const int code = -(e + 1), first = code >> 7, cnt = code & 127;
@@ -632,7 +666,7 @@ __device__ __forceinline__ void other_trace(const DevScene& sc, V3 o, V3 d, doub
       } else {
         t_hi = f32_up(h.t);
       }
-      e = sp > 0 ? stk[--sp] : kBvhEmpty;
+      e = pop();
     }
   }
 }
