@@ -13,6 +13,11 @@ hit records, a 24x16 frame and the counters.
 Pin 4: on four rtamd.scenes.fuzz seeds that together hold all five pattern
 kinds, each with and without a pattern transform (asserted from descs_bytes),
 its 24x16 frame and counters equal liboracle's bit for bit.
+Pin 5: on the tie worlds of tests/tie_worlds.py (intersections that tie bit for
+bit, where the order of the world's list decides the hit, n1 and n2) the two
+restatements of that order agree: the frame, the counters, the hit records of
+the authored rays and color_at at depths 0 and 3 equal liboracle's bit for bit;
+on the triangle grid of the `mesh` world the checker equals the mesh checker.
 """
 import math
 import random
@@ -255,3 +260,49 @@ def test_checker_patterned_frame_and_counters_equal_the_oracle_bitwise(rt, oracl
     oimg, ost = oracle.OracleWorld.from_world(w).render(cam.desc_bytes(), depth)
     assert img.tobytes() == oimg.tobytes(), np.abs(img - oimg).max()
     assert st == {k: ost[k] for k in st}
+
+
+# ---------------------------------------------------------------- ties: the stable order, stated twice
+import tie_worlds  # noqa: E402
+
+
+@pytest.mark.parametrize("name", tie_worlds.ORACLE_WORLDS)
+def test_checker_equals_oracle_on_tie_worlds(rt, oracle, name):
+    """Where roots tie bit for bit the reference's order decides (world order, a group's children in
+    order, also after divide; t1 before t2): the checker's stable sort and the oracle's stable merge
+    sort are two independent restatements of it, held to each other here."""
+    tw = tie_worlds.build(rt, name)
+    ref, ow = csg_ref.CsgRef.from_world(tw.w), oracle.OracleWorld.from_world(tw.w)
+    cls = tie_worlds.classify(ref, tw.rays)
+    assert cls["H"].sum() >= 32  # (the floors proper: tests/test_tie_worlds.py)
+    got = ref.hit_batch(tw.rays)
+    want = np.array([ow.hit(r[:3], r[3:]) for r in tw.rays])
+    assert got.tobytes() == want.tobytes(), int((got != want).any(axis=1).sum())
+    for depth in (0, tw.depth):
+        ref.counts = dict.fromkeys(csg_ref.COUNTERS, 0)
+        col = ref.color_at_batch(tw.rays, depth)
+        ocol, ost = ow.color_at_batch(tw.rays, depth)
+        assert col.tobytes() == ocol.tobytes(), (depth, int((col != ocol).any(axis=1).sum()))
+        assert ref.counts == {k: ost[k] for k in ref.counts}, depth
+    img, st = ref.render(tw.cam.desc_bytes(), tw.depth)
+    oimg, ost = ow.render(tw.cam.desc_bytes(), tw.depth)
+    assert img.tobytes() == oimg.tobytes(), np.abs(img - oimg).max()
+    assert st == {k: ost[k] for k in st}
+    assert st["rays_reflect"] > 0 and st["rays_refract"] > 0
+
+
+def test_checker_equals_the_mesh_checker_on_the_tie_grid(rt):
+    """The `mesh` tie world without its two cubes (the mesh checker takes spheres, planes and
+    triangles): 64 axis-aligned triangles whose shared edges and corners tie."""
+    tw = tie_worlds.build(rt, "mesh_bare")
+    ref, mref = csg_ref.CsgRef.from_world(tw.w), mesh_ref.MeshRef.from_world(tw.w)
+    assert tie_worlds.classify(ref, tw.rays)["H"].sum() >= 32
+    got, want = ref.hit_batch(tw.rays), mref.hit_batch(tw.rays)
+    assert got.tobytes() == want.tobytes()
+    for depth in (0, tw.depth):
+        ref.counts, mref.counts = dict.fromkeys(csg_ref.COUNTERS, 0), dict.fromkeys(csg_ref.COUNTERS, 0)
+        assert ref.color_at_batch(tw.rays, depth).tobytes() == mref.color_at_batch(tw.rays, depth).tobytes()
+        assert ref.counts == mref.counts
+    img, st = ref.render(tw.cam.desc_bytes(), tw.depth)
+    mimg, mst = mref.render(tw.cam.desc_bytes(), tw.depth)
+    assert img.tobytes() == mimg.tobytes() and st == mst and ref.csg_ties == 0
