@@ -10,7 +10,8 @@ kind of shape is refused.
 
 How it computes: Python floats, or element-wise numpy over the shapes of one
 kind (both IEEE binary64, never fused); no dot / matmul / einsum / sum;
-math.pow and math.sqrt / numpy.sqrt only. Every ray builds the reference's
+math.pow and math.sqrt / numpy.sqrt only; where Python deviates from IEEE it
+is wrapped (`floor`, `fmod`, `as_isize`, `div`). Every ray builds the reference's
 full intersection list (World::intersect, world.rs:31-38), sorts it stably
 (intersection.rs:108-116, as the oracle does) and runs the `containers` walk
 of prepare_computations literally (intersection.rs:63-90); none of the
@@ -70,9 +71,18 @@ def cross(a, b):  # vector.rs:103-109
     return (a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0])
 
 
+def div(a, b):  # `/` on an f64 (Python raises where IEEE gives an inf or a NaN: a zero divisor)
+    try:
+        return a / b
+    except ZeroDivisionError:
+        if a != a or a == 0.0:
+            return float("nan")
+        return math.copysign(INF, a) * math.copysign(1.0, b)
+
+
 def normalize(a):  # vector.rs:21-28
     m = math.sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2])
-    return (a[0] / m, a[1] / m, a[2] / m)
+    return (div(a[0], m), div(a[1], m), div(a[2], m))
 
 
 def reflect(v, n):  # vector.rs:30-32: self - normal * 2.0 * dot(self, normal)
@@ -132,12 +142,12 @@ def smooth_normal(n1, n2, n3, u, v):  # smooth_triangle.rs:103-105
 def schlick(eyev, normalv, n1, n2):  # intersection.rs:147-162
     cos = dot(eyev, normalv)
     if n1 > n2:
-        n = n1 / n2
+        n = div(n1, n2)
         sin2_t = n * n * (1.0 - cos * cos)
         if sin2_t > 1.0:
             return 1.0
         cos = math.sqrt(1.0 - sin2_t)
-    q = (n1 - n2) / (n1 + n2)
+    q = div(n1 - n2, n1 + n2)
     r0 = q * q  # powi(2)
     x = 1.0 - cos
     return r0 + (1.0 - r0) * (x * ((x * x) * (x * x)))  # powi(5): x * (x^2)^2
@@ -186,13 +196,19 @@ def pattern_color_at(kind, a, b, p):
     raise ValueError("mesh_ref: bad pattern kind")
 
 
-def pattern_color_at_shape(kind, a, b, pattern_inverse, shape_inverse, world_point):  # pattern/mod.rs:39-49
+def pattern_color_at_shape(kind, a, b, pattern_inverse, shape_inverse, world_point, events=None, tag=None):  # pattern/mod.rs:39-49
     object_point = mat_point(shape_inverse, world_point)
     pattern_point = mat_point(pattern_inverse, object_point)
+    if events is not None:
+        events.append(("pattern", kind, pattern_point, tag))
     return pattern_color_at(kind, a, b, pattern_point)
 
 
 class MeshRef:
+    # a list to record in, or None: ("pattern", kind, pattern point, object) per Pattern::color_at_shape, ("lighting", {...})
+    # per Material::lighting, ("shade", {...}) per World::shade_hit (what tests/test_shading_edges.py counts)
+    events = None
+
     def __init__(self, descs_bytes, groups_bytes=b"", shape_groups=None, triangles_bytes=b"", lights_bytes=b""):
         self.s = np.frombuffer(descs_bytes, dtype=SHAPE)
         self.g = np.frombuffer(groups_bytes, dtype=GROUP)
@@ -385,13 +401,20 @@ class MeshRef:
             color = pattern_color_at_shape(int(s["pattern_kind"]), tuple(float(x) for x in s["pattern_a"]),
                                            tuple(float(x) for x in s["pattern_b"]),
                                            [float(x) for x in s["pattern_inverse"]], [float(x) for x in s["inverse"]],
-                                           point)
+                                           point, self.events, i)
         else:
             color = tuple(float(x) for x in s["color"])
         intensity = tuple(float(x) for x in L[3:])
         effective = (color[0] * intensity[0], color[1] * intensity[1], color[2] * intensity[2])
         lightv = normalize(sub(tuple(float(x) for x in L[:3]), point))
         ambient = scale(effective, float(s["ambient"]))
+        ev = None
+        if self.events is not None:
+            ev = {"object": i, "in_shadow": bool(in_shadow), "patterned": int(s["pattern_kind"]) != PATTERN_NONE,
+                  "ambient": ambient, "intensity": intensity, "specular": float(s["specular"]),
+                  "shininess": float(s["shininess"]), "light_dot_normal": dot(lightv, normalv),
+                  "reflect_dot_eye": None, "diffuse_term": None, "specular_term": None}
+            self.events.append(("lighting", ev))
         if in_shadow:
             return ambient
         light_dot_normal = dot(lightv, normalv)
@@ -408,6 +431,8 @@ class MeshRef:
                 except OverflowError:  # f64::powf gives inf (an unnormalised eye vector)
                     factor = INF
                 specular = scale(scale(intensity, float(s["specular"])), factor)
+            if ev is not None:
+                ev["reflect_dot_eye"], ev["diffuse_term"], ev["specular_term"] = reflect_dot_eye, diffuse, specular
         return add(add(ambient, diffuse), specular)
 
     def color_at(self, o, d, remaining, kind="rays_primary"):  # world.rs:70-81
@@ -426,21 +451,33 @@ class MeshRef:
             shadowed = self.is_shadowed(c["over"], li)
             surface = add(surface, self.lighting(i, self.lights[li], c["over"], c["eyev"], c["normalv"], shadowed))
         refl_m, transp = float(s["reflective"]), float(s["transparency"])
+        ev = None
+        if self.events is not None:
+            ev = {"object": i, "remaining": remaining, "reflective": refl_m, "transparency": transp, "n1": c["n1"],
+                  "n2": c["n2"], "cos_i": dot(c["eyev"], c["normalv"]), "reflect": False, "refract": False,
+                  "sin2_t": None, "schlick": None}
+            self.events.append(("shade", ev))
         if abs(refl_m - 0.0) < EPSILON or remaining == 0:  # world.rs:107-114
             reflected = (0.0, 0.0, 0.0)
         else:
+            if ev is not None:
+                ev["reflect"] = True
             reflected = scale(self.color_at(c["over"], c["reflectv"], remaining - 1, "rays_reflect"), refl_m)
         refracted = (0.0, 0.0, 0.0)  # world.rs:116-134
         if not (abs(transp - 0.0) < EPSILON or remaining == 0):
-            n_ratio = c["n1"] / c["n2"]
+            n_ratio = div(c["n1"], c["n2"])
             cos_i = dot(c["eyev"], c["normalv"])
             sin2_t = n_ratio * n_ratio * (1.0 - cos_i * cos_i)
+            if ev is not None:
+                ev["sin2_t"], ev["refract"] = sin2_t, not sin2_t > 1.0
             if not sin2_t > 1.0:
                 cos_t = math.sqrt(1.0 - sin2_t)
                 direction = sub(scale(c["normalv"], n_ratio * cos_i - cos_t), scale(c["eyev"], n_ratio))
                 refracted = scale(self.color_at(c["under"], direction, remaining - 1, "rays_refract"), transp)
         if refl_m > 0.0 and transp > 0.0:  # world.rs:58-67
             r = schlick(c["eyev"], c["normalv"], c["n1"], c["n2"])
+            if ev is not None:
+                ev["schlick"] = r
             return add(add(surface, scale(reflected, r)), scale(refracted, 1.0 - r))
         return add(add(surface, reflected), refracted)
 
