@@ -506,6 +506,49 @@ int rt_render_png(const rt_scene* scene, const rt_camera_desc* camera,
                   uint32_t max_depth, uint32_t aa_samples, uint8_t* out, size_t cap,
                   size_t* out_len, rt_stats* stats);
 
+/* ---- output: compressed PNG ------------------------------------------------ */
+
+/* The same image in a PNG whose zlib stream is compressed (DESIGN.md "Output:
+ * compressed PNG"): every row carries the PNG filter with the least sum of
+ * absolute differences, the filtered image is cut into segments of whole rows,
+ * max(1, RT_PNG_DEFLATE_SEGMENT / (3 * width + 1)) each, and every segment is
+ * one dynamic-Huffman deflate block over literals and run-length matches
+ * (distance 1, zlib's Z_RLE tokens) closed on a byte boundary, or stored
+ * blocks where that would not be smaller. One fixed file per canvas: the three
+ * encoders below write the same bytes. The length depends on the pixels.
+ * rt_png_deflate_bound returns a capacity that always suffices (every segment
+ * stored), or 0 exactly where rt_png_size does; the encoders refuse such a
+ * canvas with RT_ERR_INVALID_ARGUMENT. The device encoders also refuse a
+ * canvas wider than RT_PNG_DEFLATE_DEVICE_MAX_WIDTH pixels (a row no longer
+ * fits a workgroup's LDS; rt_canvas_to_png_deflate takes any width). */
+#define RT_PNG_DEFLATE_SEGMENT 16384
+#define RT_PNG_DEFLATE_DEVICE_MAX_WIDTH 8533
+size_t rt_png_deflate_bound(uint32_t width, uint32_t height);
+
+/* A host canvas into `out` (cap bytes). out == NULL: *out_len receives the
+ * bound and nothing is encoded. Otherwise *out_len receives the file's actual
+ * length; a cap of at least the bound always succeeds, a smaller one succeeds
+ * if the file fits and returns RT_ERR_BUFFER_TOO_SMALL (with the needed length
+ * in *out_len) if it does not. */
+int rt_canvas_to_png_deflate(const double* rgb, uint32_t width, uint32_t height,
+                             uint8_t* out, size_t cap, size_t* out_len);
+
+/* A DEVICE canvas into DEVICE memory `d_out` (cap bytes) on `stream` (NULL =
+ * the default stream), with the conventions above; the bytes are those
+ * rt_canvas_to_png_deflate writes, and no byte of d_out beyond the file's
+ * length (none at all when it does not fit) is written. Returns after the file
+ * is complete. */
+int rt_canvas_to_png_deflate_device(const double* d_rgb, uint32_t width, uint32_t height,
+                                    uint8_t* d_out, size_t cap, size_t* out_len, void* stream);
+
+/* rt_render_png with the compressed file: rendered and encoded on the device,
+ * the length read back first, then one copy of that many bytes to `out`.
+ * out == NULL: the bound, and nothing is rendered. With a cap below the bound
+ * the frame is rendered before the call can tell whether the file fits. */
+int rt_render_png_deflate(const rt_scene* scene, const rt_camera_desc* camera,
+                          uint32_t max_depth, uint32_t aa_samples, uint8_t* out,
+                          size_t cap, size_t* out_len, rt_stats* stats);
+
 /* ---- host buffers ------------------------------------------------------------ */
 
 /* Page-locked host memory for the outputs of the host-buffer entry points

@@ -509,6 +509,22 @@ class Canvas {
     if (!f || !f.write(png.data(), (std::streamsize)png.size()))
       throw std::runtime_error("Canvas::save: cannot write `" + path + "`");
   }
+  // the same image in a compressed PNG (rt_canvas_to_png_deflate: filters, run-length
+  // matches, a dynamic Huffman code per segment)
+  std::string to_png_deflate() const {
+    size_t len = 0;
+    std::string s(rt_png_deflate_bound((uint32_t)w_, (uint32_t)h_), '\0');
+    check(rt_canvas_to_png_deflate(px_.get(), (uint32_t)w_, (uint32_t)h_, (uint8_t*)&s[0], s.size(), &len),
+          "rt_canvas_to_png_deflate");
+    s.resize(len);
+    return s;
+  }
+  void save_compressed(const std::string& path) const {
+    const std::string png = to_png_deflate();
+    std::ofstream f(path, std::ios::binary);
+    if (!f || !f.write(png.data(), (std::streamsize)png.size()))
+      throw std::runtime_error("Canvas::save_compressed: cannot write `" + path + "`");
+  }
 
  private:
   size_t idx(size_t x, size_t y) const {  // canvas.rs:44-48 (asserts -> exceptions)
@@ -819,6 +835,33 @@ class Camera {
     size_t len = 0;
     check(rt_render_png(world.scene(), &desc_, max_depth, aa_samples, (uint8_t*)buf, bound, &len, stats),
           "rt_render_png");
+    take((const char*)buf, len);
+  }
+  // render_png's image in the compressed PNG (rt_render_png_deflate), through a pooled pinned
+  // block of the bound; only the file's actual length crosses the link.
+  std::string render_png_deflate(const World& world, unsigned max_depth = 5, unsigned aa_samples = 1,
+                                 rt_stats* stats = nullptr) const {
+    std::string s;
+    render_png_deflate_with(world, max_depth, aa_samples, stats, [&](const char* p, size_t n) { s.assign(p, n); });
+    return s;
+  }
+  template <typename F>
+  void render_png_deflate_with(const World& world, unsigned max_depth, unsigned aa_samples, rt_stats* stats,
+                               F&& take) const {
+    const size_t bound = rt_png_deflate_bound(desc_.hsize, desc_.vsize);  // (0: rt_render_png_deflate says why)
+    struct Block {
+      void* p;
+      ~Block() { rt_host_buffer_free(p); }
+    } blk{bound ? rt_host_buffer_alloc(bound) : nullptr};
+    std::string fallback;
+    char* buf = (char*)blk.p;
+    if (!buf) {
+      fallback.resize(std::max<size_t>(bound, 1));
+      buf = &fallback[0];
+    }
+    size_t len = 0;
+    check(rt_render_png_deflate(world.scene(), &desc_, max_depth, aa_samples, (uint8_t*)buf, bound, &len, stats),
+          "rt_render_png_deflate");
     take((const char*)buf, len);
   }
   RenderOpts render_opts;

@@ -86,13 +86,15 @@ class SceneParser {
   // lib.rs:267-284 renders and saves through PngExporter: a path ending in `.png` (any
   // letter case) gets that PNG (rendered and encoded on the device: rt_render_png; it
   // decodes to render(...)'s quantised canvas); any other path gets the PPM
-  // (image/ppm.rs; rt_render_ppm; bytes = render(...).to_ppm())
-  void render_to(const std::string& path, unsigned max_depth = 5) const {
+  // (image/ppm.rs; rt_render_ppm; bytes = render(...).to_ppm()). `compress`: the PNG is the
+  // compressed one (rt_render_png_deflate); a PPM is not affected.
+  void render_to(const std::string& path, unsigned max_depth = 5, bool compress = false) const {
     if (!scene_.camera) throw SceneParserError("missing required key `camera`");
     auto w = build_world();
     std::string ext = path.size() >= 4 ? path.substr(path.size() - 4) : std::string();
     for (char& ch : ext) ch = (char)std::tolower((unsigned char)ch);
-    const std::string file = ext == ".png"                     ? scene_.camera->render_png(*w, max_depth)
+    const std::string file = ext == ".png" && compress         ? scene_.camera->render_png_deflate(*w, max_depth)
+                             : ext == ".png"                   ? scene_.camera->render_png(*w, max_depth)
                              : scene_.camera->hsize() <= 12288 ? scene_.camera->render_ppm(*w, max_depth)
                                                                : scene_.camera->render(*w, max_depth).to_ppm();
     std::ofstream f(path, std::ios::binary);

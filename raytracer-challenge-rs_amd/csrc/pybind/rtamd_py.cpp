@@ -86,6 +86,8 @@ extern "C" int rtamd_nccl_gather_f64(const double* send, double* recv, size_t co
 extern "C" int rtamd_nccl_comm_destroy(void* comm);
 extern "C" int rtamd_wf_profile(const rt_scene* s, int enable, double out[40]);
 extern "C" int rtamd_wf_gen_counts(const rt_scene* s, unsigned* out, int max);
+extern "C" int rtamd_pngz_kernel_times(const double* d_rgb, uint32_t width, uint32_t height, uint8_t* d_out, size_t cap,
+                                       float* ms, void* stream);
 extern "C" int rtamd_wf_plan(const rt_scene* s, long long out[14]);
 extern "C" int rtamd_csg_plan(const rt_scene* s, long long out[6]);
 extern "C" int rtamd_scene_tuning_set(const rt_scene* s, const char* key, int value);
@@ -365,6 +367,8 @@ PYBIND11_MODULE(_rtamd, m) {
       .def("to_ppm", [](const Canvas& c) { return py::bytes(c.to_ppm()); })
       .def("to_png", [](const Canvas& c) { return py::bytes(c.to_png()); })
       .def("save", &Canvas::save, py::arg("path"))
+      .def("to_png_deflate", [](const Canvas& c) { return py::bytes(c.to_png_deflate()); })
+      .def("save_compressed", &Canvas::save_compressed, py::arg("path"))
       .def("to_numpy", [](const Canvas& c) {
         py::array_t<double> a({(py::ssize_t)c.height(), (py::ssize_t)c.width(), (py::ssize_t)3});
         std::memcpy(a.mutable_data(), c.data(), c.width() * c.height() * 3 * sizeof(double));
@@ -435,6 +439,46 @@ PYBIND11_MODULE(_rtamd, m) {
     return len;
   }, py::arg("d_rgb"), py::arg("width"), py::arg("height"), py::arg("d_out"), py::arg("cap"), py::arg("stream") = 0);
   m.def("png_size", &rt_png_size, py::arg("width"), py::arg("height"));
+  // the compressed PNG (rt_canvas_to_png_deflate) of an (h, w, 3) array
+  m.def("canvas_to_png_deflate", [](py::array_t<double, py::array::c_style | py::array::forcecast> rgb) {
+    if (rgb.ndim() != 3 || rgb.shape(2) != 3) throw std::invalid_argument("expected (h, w, 3)");
+    const uint32_t h = (uint32_t)rgb.shape(0), w = (uint32_t)rgb.shape(1);
+    size_t bound = 0, len = 0;
+    check(rt_canvas_to_png_deflate(nullptr, w, h, nullptr, 0, &bound), "rt_canvas_to_png_deflate");
+    PyObject* obj = PyBytes_FromStringAndSize(nullptr, (Py_ssize_t)bound);
+    if (!obj) throw py::error_already_set();
+    int rc;
+    {
+      py::gil_scoped_release nogil;
+      rc = rt_canvas_to_png_deflate(rgb.data(), w, h, (uint8_t*)PyBytes_AS_STRING(obj), bound, &len);
+    }
+    if (rc != RT_OK) {
+      Py_DECREF(obj);
+      check(rc, "rt_canvas_to_png_deflate");
+    }
+    if (_PyBytes_Resize(&obj, (Py_ssize_t)len) != 0) throw py::error_already_set();
+    return py::reinterpret_steal<py::bytes>(obj);
+  });
+  // ... of a device canvas into a device buffer (pointers as integers); returns the file's
+  // length (d_out == 0: the bound)
+  m.def("canvas_to_png_deflate_device", [](uintptr_t d_rgb, uint32_t w, uint32_t h, uintptr_t d_out, size_t cap,
+                                           uintptr_t stream) {
+    size_t len = 0;
+    {
+      py::gil_scoped_release nogil;
+      check(rt_canvas_to_png_deflate_device((const double*)d_rgb, w, h, (uint8_t*)d_out, cap, &len, (void*)stream),
+            "rt_canvas_to_png_deflate_device");
+    }
+    return len;
+  }, py::arg("d_rgb"), py::arg("width"), py::arg("height"), py::arg("d_out"), py::arg("cap"), py::arg("stream") = 0);
+  m.def("png_deflate_bound", &rt_png_deflate_bound, py::arg("width"), py::arg("height"));
+  // (profiling aid) stream-event times, ms, of the device encoder's four kernels
+  m.def("_pngz_kernel_times", [](uintptr_t d_rgb, uint32_t w, uint32_t h, uintptr_t d_out, size_t cap, uintptr_t stream) {
+    float ms[4] = {};
+    check(rtamd_pngz_kernel_times((const double*)d_rgb, w, h, (uint8_t*)d_out, cap, ms, (void*)stream),
+          "rtamd_pngz_kernel_times");
+    return py::make_tuple(ms[0], ms[1], ms[2], ms[3]);
+  }, py::arg("d_rgb"), py::arg("width"), py::arg("height"), py::arg("d_out"), py::arg("cap"), py::arg("stream") = 0);
   m.def("quantize_u8", [](py::array_t<double, py::array::c_style | py::array::forcecast> v) {
     py::array_t<uint8_t> o(v.size());
     check(rt_quantize_u8(v.data(), (size_t)v.size(), o.mutable_data()), "rt_quantize_u8");
@@ -624,6 +668,35 @@ PYBIND11_MODULE(_rtamd, m) {
         check(rc, "rt_render_png");
         return len;
       }, py::arg("world"), py::arg("out"), py::arg("max_depth") = 5, py::arg("aa_samples") = 1)
+      // render_png's image in the compressed PNG (rt_render_png_deflate)
+      .def("render_png_deflate", [](const Camera& c, const World& w, unsigned max_depth, unsigned aa_samples,
+                                    bool want_stats) {
+        rt_stats st{};
+        py::object out;
+        {
+          py::gil_scoped_release nogil;
+          c.render_png_deflate_with(w, max_depth, aa_samples, want_stats ? &st : nullptr, [&](const char* p, size_t n) {
+            py::gil_scoped_acquire gil;
+            out = py::bytes(p, n);
+          });
+        }
+        return py::make_tuple(out, stats_dict(st));
+      }, py::arg("world"), py::arg("max_depth") = 5, py::arg("aa_samples") = 1, py::arg("want_stats") = false)
+      // the same into the caller's buffer: returns the file's length
+      .def("render_png_deflate_into", [](const Camera& c, const World& w, py::buffer out, unsigned max_depth,
+                                         unsigned aa_samples) {
+        py::buffer_info bi = out.request(true);
+        if (bi.ndim != 1 || bi.itemsize != 1) throw std::invalid_argument("expected a writable 1-D byte buffer");
+        size_t len = 0;
+        int rc;
+        {
+          py::gil_scoped_release nogil;
+          rc = rt_render_png_deflate(w.scene(), &c.desc(), max_depth, aa_samples, (uint8_t*)bi.ptr, (size_t)bi.size,
+                                     &len, nullptr);
+        }
+        check(rc, "rt_render_png_deflate");
+        return len;
+      }, py::arg("world"), py::arg("out"), py::arg("max_depth") = 5, py::arg("aa_samples") = 1)
       .def_readwrite("render_opts", &Camera::render_opts, py::return_value_policy::reference_internal)
       .def("render_multithreaded", [](const Camera& c, const World& w, unsigned max_depth, bool want_stats,
                                       py::object exhaustive) {
@@ -764,7 +837,8 @@ PYBIND11_MODULE(_rtamd, m) {
         }
         return py::make_tuple(std::unique_ptr<Canvas>(out), stats_dict(st));
       }, py::arg("max_depth") = 5)
-      .def("render_to", &SceneParser::render_to, py::arg("path"), py::arg("max_depth") = 5);
+      .def("render_to", &SceneParser::render_to, py::arg("path"), py::arg("max_depth") = 5,
+           py::arg("compress") = false);
   m.def("_wf_gen_counts", [](const World& w) {
     unsigned o[66] = {0};
     const int n = rtamd_wf_gen_counts(w.scene(), o, 66);

@@ -37,6 +37,7 @@
 #include "rt_kernels.hpp"
 #include "rt_layout.hpp"
 #include "rt_ppm_dev.hpp"
+#include "rt_png_deflate_dev.hpp"
 #include "rt_png_dev.hpp"
 #include "rt_wavefront.hpp"
 
@@ -143,6 +144,8 @@ struct rt_scene {
     size_t ppm_rows_cap = 0;  // rows
     uint8_t* d_png = nullptr;  // rt_render_png: the file, then the encoder's per-segment words
     size_t png_cap = 0;
+    uint8_t* d_pngz = nullptr;  // rt_render_png_deflate: the file (its bound), then the encoder's work area
+    size_t pngz_cap = 0;
     void* h_stage[2] = {nullptr, nullptr};  // device-to-host copies into caller memory: two pinned chunks
     hipEvent_t stage_ev[2] = {nullptr, nullptr};
     // banded host renders (render_banded): a stream per band after the first, and the
@@ -217,7 +220,7 @@ struct rt_scene {
         (void)hipStreamDestroy(c.stream);
       }
       (void)hipFree(c.d_out); (void)hipFree(c.d_in); (void)hipFree(c.d_ppm); (void)hipFree(c.d_ppm_rows);
-      (void)hipFree(c.d_png);
+      (void)hipFree(c.d_png); (void)hipFree(c.d_pngz);
       for (int k = 0; k < 2; ++k) {
         if (c.h_stage[k]) (void)hipHostFree(c.h_stage[k]);
         if (c.stage_ev[k]) (void)hipEventDestroy(c.stage_ev[k]);

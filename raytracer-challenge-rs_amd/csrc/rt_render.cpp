@@ -601,6 +601,145 @@ int rt_canvas_to_png_device(const double* d_rgb, uint32_t width, uint32_t height
   });
 }
 
+// the refusal of the device encoder's own limits, after rtamd_png_check
+static int pngz_device_check(uint32_t W, uint32_t H) {
+  if (W > kPngzMaxWidth)
+    return fail(RT_ERR_INVALID_ARGUMENT,
+                "compressed PNG: canvas wider than the device encoder's row (use rt_canvas_to_png_deflate)");
+  if (!pngz_device_encodable(W, H))
+    return fail(RT_ERR_INVALID_ARGUMENT, "compressed PNG: the IDAT payload could exceed 2^31 - 1 bytes");
+  return RT_OK;
+}
+
+int rt_render_png_deflate(const rt_scene* scene, const rt_camera_desc* camera, uint32_t max_depth,
+                          uint32_t aa_samples, uint8_t* out, size_t cap, size_t* out_len, rt_stats* stats) {
+  return guarded([&]() -> int {
+  if (!scene || !camera || !out_len) return fail(RT_ERR_INVALID_ARGUMENT, "null pointer");
+  if (!valid_aa(aa_samples)) return fail(RT_ERR_INVALID_ARGUMENT, "aa_samples must be 1, 2, 4, 8 or 16");
+  const uint32_t W = camera->hsize, H = camera->vsize;
+  if (const int bad = rtamd_png_check(W, H)) return bad;
+  const uint64_t n_pix = (uint64_t)W * H;
+  if (n_pix * aa_samples >= (1ull << 31)) return fail(RT_ERR_INVALID_ARGUMENT, "canvas too large for one launch");
+  const size_t bound = (size_t)rtpngz::bound(W, H);
+  *out_len = bound;
+  if (!out) return RT_OK;
+  if (const int bad = pngz_device_check(W, H)) return bad;
+  rt_scene* s = const_cast<rt_scene*>(scene);
+  std::unique_lock<std::mutex> lk(s->mu);
+  auto t0 = std::chrono::steady_clock::now();
+  RT_DEVICE(s->device);
+  CtxLease cx{s, lk};
+  RT_TAKE_CTX(cx);
+  rt_scene::HostCtx* c = cx.c;
+  int rc = ensure_dev_buffer(&c->d_out, &c->out_cap, n_pix * 3);
+  if (rc != RT_OK) return rc;
+  const size_t work_at = (bound + 15) & ~(size_t)15, need = work_at + pngz_work_bytes(W, H);
+  if (c->pngz_cap < need) {
+    if (c->d_pngz) (void)hipFree(c->d_pngz);
+    c->d_pngz = nullptr;
+    c->pngz_cap = 0;
+    RT_HIP(hipMalloc((void**)&c->d_pngz, need));
+    c->pngz_cap = need;
+  }
+  if (!c->h_len) RT_HIP(hipHostMalloc((void**)&c->h_len, sizeof(unsigned long long), hipHostMallocDefault));
+  struct Drain {  // no kernel or copy of this call outlives it (the context goes back to the pool)
+    hipStream_t st;
+    ~Drain() {
+      if (hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
+    }
+  } drain{c->stream};
+  const WfJob job = WfJob::camera_shard(to_dev_camera(*camera), (uint32_t)(n_pix * aa_samples), aa_samples, max_depth,
+                                        c->d_out, H);
+  // As rt_render_ppm: the render, the encoder and the file's length in one pass of the stream,
+  // one wait, then the workspace's overflow record; a frame that outgrew its arenas is rendered
+  // and encoded again. The file is encoded into the device buffer of the bound, so the
+  // caller's capacity only decides the copy.
+  PinGuard pin(s, &lk);
+  RenderCall call(&lk);
+  call.stats = call.time = stats != nullptr;
+  if (!stats) call.keep_pin = &pin;
+  RenderResult r;
+  if ((rc = run_render(s, job, c->stream, call, &r)) != RT_OK) return rc;
+  auto encode = [&]() -> int {
+    RT_HIP(pngz_encode_device(c->d_out, W, H, c->d_pngz, bound, c->d_pngz + work_at, c->stream));
+    RT_HIP(hipMemcpyAsync(c->h_len, c->d_pngz + work_at, sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                          c->stream));
+    lk.unlock();
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    lk.lock();
+    if (e != hipSuccess) return fail(RT_ERR_HIP, std::string("rt_render_png_deflate: ") + hipGetErrorString(e));
+    return RT_OK;
+  };
+  if ((rc = encode()) != RT_OK) return rc;
+  bool over = false;
+  if ((rc = settle(pin, s->sizing, &over)) != RT_OK) return rc;
+  if (over) {  // (the canvas was poisoned: render it again, growing the arenas until it fits)
+    RenderCall again(&lk);
+    again.sync = true;
+    if ((rc = run_render(s, job, c->stream, again)) != RT_OK) return rc;
+    if ((rc = encode()) != RT_OK) return rc;
+  }
+  const int d2h = s->tune.d2h;
+  lk.unlock();
+  *out_len = (size_t)*c->h_len;
+  if (cap < *out_len) return fail(RT_ERR_BUFFER_TOO_SMALL, "PNG buffer too small");
+  if ((rc = copy_to_host(c, d2h, out, c->d_pngz, *out_len, c->stream)) != RT_OK) return rc;
+  if (stats)
+    fill_stats(stats, r.stats, r.ms,
+               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+  return RT_OK;
+  });
+}
+
+int rt_canvas_to_png_deflate_device(const double* d_rgb, uint32_t width, uint32_t height, uint8_t* d_out, size_t cap,
+                                    size_t* out_len, void* stream) {
+  return guarded([&]() -> int {
+  if (!out_len) return fail(RT_ERR_INVALID_ARGUMENT, "null pointer");
+  if (const int bad = rtamd_png_check(width, height)) return bad;
+  *out_len = (size_t)rtpngz::bound(width, height);
+  if (!d_out) return RT_OK;  // the bound alone: the length depends on the pixels
+  if (!d_rgb) return fail(RT_ERR_INVALID_ARGUMENT, "null pointer");
+  if (const int bad = pngz_device_check(width, height)) return bad;
+  hipStream_t st = (hipStream_t)stream;
+  void* work = nullptr;
+  RT_HIP(hipMallocAsync(&work, pngz_work_bytes(width, height), st));
+  hipError_t e = pngz_encode_device(d_rgb, width, height, d_out, cap, work, st);
+  unsigned long long len = 0;
+  if (e == hipSuccess) e = hipMemcpyAsync(&len, work, sizeof len, hipMemcpyDeviceToHost, st);
+  (void)hipFreeAsync(work, st);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e != hipSuccess)
+    return fail(RT_ERR_HIP, std::string("rt_canvas_to_png_deflate_device: ") + hipGetErrorString(e));
+  *out_len = (size_t)len;
+  if (cap < *out_len) return fail(RT_ERR_BUFFER_TOO_SMALL, "PNG buffer too small");
+  return RT_OK;
+  });
+}
+
+// (profiling aid, tools/png_deflate_probe.py) rt_canvas_to_png_deflate_device with stream
+// events between its kernels: ms[0..3] = pngz_encode, pngz_scan, pngz_pack, pngz_finish
+extern "C" int rtamd_pngz_kernel_times(const double* d_rgb, uint32_t width, uint32_t height, uint8_t* d_out,
+                                       size_t cap, float* ms, void* stream) {
+  return guarded([&]() -> int {
+  if (!d_rgb || !d_out || !ms) return fail(RT_ERR_INVALID_ARGUMENT, "null pointer");
+  if (const int bad = rtamd_png_check(width, height)) return bad;
+  if (const int bad = pngz_device_check(width, height)) return bad;
+  hipStream_t st = (hipStream_t)stream;
+  hipEvent_t ev[5] = {};
+  void* work = nullptr;
+  hipError_t e = hipMalloc(&work, pngz_work_bytes(width, height));
+  for (int k = 0; k < 5 && e == hipSuccess; ++k) e = hipEventCreate(&ev[k]);
+  if (e == hipSuccess) e = pngz_encode_device(d_rgb, width, height, d_out, cap, work, st, ev);
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  for (int k = 0; k < 4 && e == hipSuccess; ++k) e = hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]);
+  for (hipEvent_t v : ev)
+    if (v) (void)hipEventDestroy(v);
+  if (work) (void)hipFree(work);
+  if (e != hipSuccess) return fail(RT_ERR_HIP, std::string("rtamd_pngz_kernel_times: ") + hipGetErrorString(e));
+  return RT_OK;
+  });
+}
+
 int rt_render(const rt_scene* scene, const rt_camera_desc* camera, uint32_t max_depth, double* out_rgb,
               rt_stats* stats) {
   return guarded([&]() -> int {
