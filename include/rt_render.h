@@ -291,6 +291,57 @@ int rt_scene_create_tree(const rt_shape_desc* shapes, size_t n_shapes,
                          const rt_triangle_desc* tris, size_t n_tris,
                          const rt_light_desc* lights, size_t n_lights, int device,
                          rt_scene** out);
+/* (ABI 6, additive) rt_scene_create_tree for a World in which shapes ARE
+ * structurally equal (the reference renders such worlds: in
+ * prepare_computations, `containers.contains(&i.object)` and `position(..)`
+ * go through PartialEq for dyn Shape, so equal shapes alias in the
+ * refractive-index walk, intersection.rs:63-90). The relation is the caller's:
+ * rt_shape_desc carries neither the bounding box nor the inverse transpose, and
+ * both take part in the derived PartialEq (the box depends on the set_transform
+ * history, geometry/mod.rs:74-85). `equal_pairs` holds n_pairs pairs (i, j),
+ * i < j, sorted by (i, j) without repeats: the pairs of shapes for which the
+ * caller's `==` holds. A pair of Spheres .. Cones that is not listed is
+ * distinct, whatever its fields; none is looked for here
+ * (rt_shapes_equal_pairs derives them). Triangles keep the other entry
+ * points' rule: two that may be structurally equal are refused, listed or not.
+ * RT_ERR_INVALID_ARGUMENT: a pair out of range, out of order or repeated, or
+ * one whose two descriptors differ in a field the derived PartialEq compares
+ * (such shapes cannot be equal).
+ * RT_ERR_DUPLICATE_SHAPES (the message says which): a connected component of
+ * the pairs that is not complete (A == B, B == C, A != C: `equal()` is
+ * |a - b| < EPSILON, not transitive; that walk needs the whole list); two
+ * Triangles or SmoothTriangles that may be equal; a pair with a primitive
+ * under a Csg.
+ * The members of each complete component (an alias class: exact and near
+ * duplicates) are intersected in a list of their own, outside every
+ * hierarchy: their cost is linear in their number, and there is no cap on it.
+ * With n_pairs == 0 the scene is rt_scene_create_tree's, without its
+ * RT_ERR_DUPLICATE_SHAPES refusal of Spheres .. Cones. */
+int rt_scene_create_aliased(const rt_shape_desc* shapes, size_t n_shapes,
+                            const int32_t* shape_node, const int32_t* shape_side,
+                            const rt_node_desc* nodes, size_t n_nodes,
+                            const rt_triangle_desc* tris, size_t n_tris,
+                            const rt_light_desc* lights, size_t n_lights,
+                            const int32_t* equal_pairs, size_t n_pairs, int device,
+                            rt_scene** out);
+/* (ABI 6, additive) The pairs rt_scene_create_aliased takes, for shapes of
+ * kinds Sphere .. Cone built the way the reference's constructors followed by
+ * at most ONE set_transform build them (a bitwise-identity `transform` stands
+ * for "never called"): the bounding box is recomputed as set_transform does
+ * (the primitive's box through the old inverse, the identity, then through
+ * `transform`; bounding_box.rs:71-89) and compared as BoundingBox's PartialEq
+ * does (point.rs:26-30), the inverse transpose follows from `inverse`.
+ * Triangles are never listed. Writes up to `cap` pairs (2 * cap int32) into
+ * out_pairs, sorted by (i, j), and the number found into *n_pairs; more than
+ * `cap` returns RT_ERR_BUFFER_TOO_SMALL with *n_pairs set (out_pairs may be
+ * NULL with cap == 0). Candidates come from a sweep over a sorted key of the
+ * Spheres .. Cones alone, so the cost is n log n plus the pairs of them within
+ * EPSILON of each other, whatever triangles the shapes hold. The caller must
+ * meet the assumption: a shape whose set_transform ran twice may have another
+ * box than the one computed here, and only the caller's own `==` knows.
+ * No device work. */
+int rt_shapes_equal_pairs(const rt_shape_desc* shapes, size_t n_shapes,
+                          int32_t* out_pairs, size_t cap, size_t* n_pairs);
 void rt_scene_destroy(rt_scene* scene);
 
 /* ---- render entry points -------------------------------------------------- */

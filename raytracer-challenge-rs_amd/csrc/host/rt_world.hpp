@@ -682,7 +682,25 @@ class World {
       const Flat f = flatten();
       auto l = light_descs();
       rt_scene* s = nullptr;
-      if (f.has_csg)
+      if (aliases_) {
+        // The pairs of structurally equal primitives. rt_shapes_equal_pairs assumes shapes built by
+        // their constructor and at most one set_transform; that is the caller's to meet (this mirror
+        // does not count the calls: a shape transformed twice may compare otherwise in the reference).
+        // Room for one pair a shape, which exact and near duplicates rarely pass: one sweep, not two.
+        size_t n_pairs = 0;
+        std::vector<int32_t> pairs(2 * f.shapes.size());
+        int rc = rt_shapes_equal_pairs(f.shapes.data(), f.shapes.size(), pairs.data(), f.shapes.size(), &n_pairs);
+        if (rc == RT_ERR_BUFFER_TOO_SMALL) {
+          pairs.resize(2 * n_pairs);
+          rc = rt_shapes_equal_pairs(f.shapes.data(), f.shapes.size(), pairs.data(), n_pairs, &n_pairs);
+        }
+        check(rc, "rt_shapes_equal_pairs");
+        // (`nodes` holds the groups without a Csg too)
+        check(rt_scene_create_aliased(f.shapes.data(), f.shapes.size(), f.shape_group.data(), f.shape_side.data(),
+                                      f.nodes.data(), f.nodes.size(), f.tris.data(), f.tris.size(), l.data(), l.size(),
+                                      pairs.data(), n_pairs, device, &s),
+              "rt_scene_create_aliased");
+      } else if (f.has_csg)
         check(rt_scene_create_tree(f.shapes.data(), f.shapes.size(), f.shape_group.data(), f.shape_side.data(),
                                    f.nodes.data(), f.nodes.size(), f.tris.data(), f.tris.size(), l.data(), l.size(),
                                    device, &s),
@@ -695,6 +713,21 @@ class World {
       scene_device_ = device;
     }
     return scene_;
+  }
+  // Opt-in (off by default: structurally equal shapes are refused, RT_ERR_DUPLICATE_SHAPES): upload
+  // through rt_scene_create_aliased with the pairs rt_shapes_equal_pairs finds, so that equal
+  // shapes alias in the containers walk as the reference's do. Changing it drops the uploaded scene.
+  void set_aliases(bool on) {
+    if (on != aliases_) drop();
+    aliases_ = on;
+  }
+  bool aliases() const { return aliases_; }
+  // upload(device) keeps the opt-in as it is (a world from the scene parser stays opted in when it
+  // moves to another device); upload(device, aliases) sets it.
+  void upload(int device = 0) { scene(device); }
+  void upload(int device, bool aliases) {
+    set_aliases(aliases);
+    scene(device);
   }
   int scene_device() const { return scene_ ? scene_device_ : -1; }
   const void* scene_handle() const { return scene_; }
@@ -728,6 +761,7 @@ class World {
   std::vector<PointLight> lights_;
   mutable rt_scene* scene_ = nullptr;
   mutable int scene_device_ = -1;
+  bool aliases_ = false;
 };
 
 // camera.rs:220-253

@@ -74,6 +74,7 @@ class SceneParser {
   // lib.rs:267-284: lights then shapes into a World, Camera::render.
   std::unique_ptr<World> build_world() const {
     auto w = std::make_unique<World>();
+    w->set_aliases(true);  // a file may place one shape twice; the reference's binary renders it
     for (const auto& l : scene_.lights) w->add_light(l);
     for (const auto& s : scene_.shapes) w->add_object(s);
     return w;

@@ -88,7 +88,7 @@ extern "C" int rtamd_wf_profile(const rt_scene* s, int enable, double out[40]);
 extern "C" int rtamd_wf_gen_counts(const rt_scene* s, unsigned* out, int max);
 extern "C" int rtamd_pngz_kernel_times(const double* d_rgb, uint32_t width, uint32_t height, uint8_t* d_out, size_t cap,
                                        float* ms, void* stream);
-extern "C" int rtamd_wf_plan(const rt_scene* s, long long out[14]);
+extern "C" int rtamd_wf_plan(const rt_scene* s, long long out[16]);
 extern "C" int rtamd_csg_plan(const rt_scene* s, long long out[6]);
 extern "C" int rtamd_scene_tuning_set(const rt_scene* s, const char* key, int value);
 extern "C" int rtamd_render_shard_host(const rt_scene* scene, const rt_camera_desc* camera, uint32_t max_depth,
@@ -503,7 +503,15 @@ PYBIND11_MODULE(_rtamd, m) {
       .def("n_lights", &World::n_lights)
       .def("object", &World::object, py::return_value_policy::reference_internal)
       .def("light", &World::light, py::return_value_policy::reference_internal)
-      .def("upload", [](const World& w, int device) { w.scene(device); }, py::arg("device") = 0)
+      // aliases=True: structurally equal shapes alias in the containers walk, as the reference's do
+      // (rt_shapes_equal_pairs + rt_scene_create_aliased); the default refuses them
+      // aliases=None (the default) leaves the world's opt-in as it is: off for a new World, on for one
+      // the scene parser built, and what an earlier upload(aliases=...) set
+      .def("upload", [](World& w, int device, py::object aliases) {
+        if (aliases.is_none()) w.upload(device);
+        else w.upload(device, aliases.cast<bool>());
+      }, py::arg("device") = 0, py::arg("aliases") = py::none())
+      .def_property_readonly("aliases", &World::aliases)
       .def_property_readonly("scene_device", &World::scene_device)  // -1: not uploaded
       .def("_scene_handle", [](const World& w) { return (uintptr_t)w.scene_handle(); })
       .def("_debug_relabel_device", &World::debug_relabel_device)
@@ -876,7 +884,7 @@ PYBIND11_MODULE(_rtamd, m) {
   // the image plans of the last render's fused launches (rt_wf_plan.hpp): generation 0's and the
   // last deeper generation's; lane -1 = none. lds_spheres / lds_deltas: the kLdsSpheres / kLdsDeltas flags
   m.def("_wf_plan", [](const World& w) {
-    long long o[14] = {0};
+    long long o[16] = {0};
     check(rtamd_wf_plan(w.scene(), o), "wf_plan");
     py::dict d;
     const char* which[2] = {"primary", "secondary"};
@@ -895,6 +903,8 @@ PYBIND11_MODULE(_rtamd, m) {
     d["triangles"] = t;
     d["n_tris"] = o[12];  // what launch_fused chooses the TRIS and CSG kernels by
     d["n_csg_units"] = o[13];
+    d["n_alias_members"] = o[14];  // ... and the ALIAS kernels by (the alias classes' members; their classes)
+    d["n_alias_classes"] = o[15];
     return d;
   }, py::arg("world"));
   // the Csg units' hierarchy (unit_trace): the scene's units, those the hierarchy holds, those left

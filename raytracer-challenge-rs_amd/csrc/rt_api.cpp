@@ -126,8 +126,9 @@ int rtamd_wf_profile(const rt_scene* cs, int enable, double out[40]) {
 // last deeper generation's. Lane -1 (and zeros): no such launch, or the render was not fused.
 // out[8..11]: the triangle hierarchy (tri_trace): its records, depth and nodes, and whether the
 // last render walked it (a fused render of a scene that has one). out[12..13]: the scene's
-// triangles and Csg units, which choose the TRIS and CSG kernels (launch_fused).
-int rtamd_wf_plan(const rt_scene* cs, long long out[14]) {
+// triangles and Csg units, which choose the TRIS and CSG kernels (launch_fused). out[14..15]: the
+// alias classes' members and the classes, which choose the ALIAS kernels.
+int rtamd_wf_plan(const rt_scene* cs, long long out[16]) {
   if (!cs || !out) return fail(RT_ERR_INVALID_ARGUMENT, "null scene or output");
   rt_scene* s = const_cast<rt_scene*>(cs);
   std::lock_guard<std::mutex> lk(s->mu);
@@ -146,6 +147,8 @@ int rtamd_wf_plan(const rt_scene* cs, long long out[14]) {
   out[11] = s->dev.n_tbvh > 0 && (pl[0]->lane >= 0 || pl[1]->lane >= 0) ? 1 : 0;
   out[12] = s->dev.n_tris;
   out[13] = s->dev.n_csg_units;
+  out[14] = s->dev.n_alias_rec;
+  out[15] = s->dev.n_alias_cls;
   return RT_OK;
 }
 

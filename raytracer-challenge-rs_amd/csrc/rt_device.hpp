@@ -501,6 +501,121 @@ __device__ __forceinline__ void csg_units(const DevScene& sc, const CsgUnit* uni
   if (skips) { skips->sph += sk.sph; skips->plane += sk.plane; skips->other += sk.other; }
 }
 
+// ----------------------------------------------------------- alias classes
+// World::intersect's share of the alias classes (rt_layout.hpp AliasClass; DESIGN.md "containers
+// walk -> top-2", "Alias classes"). In the walk of prepare_computations `contains` and `position`
+// compare by structural equality, so the members of a class are one `containers` entry: each
+// intersection of any member before the hit toggles it. It is there at the hit iff the class has
+// an odd number of roots t < 0 over ALL its members, at the place of the last of them by
+// (t, key); its refractive index is any member's (equal shapes have bit-equal materials). So per
+// class, in registers: the count of roots t < 0 and the greatest (t, key) among them, one
+// push_container after the last member. The closest hit is each member's own business: every
+// root t >= 0 competes by (t, key) with its own object index. A hit on a member finds its object
+// in `containers` iff the class is there (`hin`).
+// Each member's roots are its kind's, operation for operation: sphere_adc's, plane_test's,
+// quad_local_intersect's; a NaN root (a sphere's, from a zero direction) is neither before the
+// hit nor a hit, as everywhere else. Shadow rays (is_shadowed asks for any blocker): every member
+// is an ordinary record. The members are in no hierarchy: every ray tests each behind its gate.
+template <bool SHADOW>
+__device__ __forceinline__ void alias_classes(const DevScene& sc, V3 o, V3 d, Hit& h, unsigned& n_disc,
+                                              GateSkips* skips) {
+  const cQuadRec rec = (cQuadRec)sc.alias_rec;
+  const AliasClass RT_CONST* cls = (const AliasClass RT_CONST*)sc.alias_cls;
+  for (int c = 0; c < sc.n_alias_cls; ++c) {
+    const int first = cls[c].first, end = first + cls[c].n;
+    int n_neg = 0, neg_k = -1;
+    double neg_t = -INFINITY;
+    bool took = false;
+    for (int j = first; j < end; ++j) {
+      const int kind = rec[j].kind;
+      if (rec[j].gate && !group_gate(sc, rec[j].gate, o, d)) {  // Group::intersect (group.rs:49-58)
+        if (skips) {
+          if (kind == 0) ++skips->sph; else if (kind == 1) ++skips->plane; else ++skips->other;
+        }
+        continue;
+      }
+      if constexpr (SHADOW) {
+        if (kind == 1) {
+          plane_test<true>(rec[j].m[4] * o.x + rec[j].m[5] * o.y + rec[j].m[6] * o.z + rec[j].m[7],
+                           rec[j].m[4] * d.x + rec[j].m[5] * d.y + rec[j].m[6] * d.z, rec[j].meta, h);
+        } else if (kind == 0) {
+          double m[12];
+#pragma unroll
+          for (int e = 0; e < 12; ++e) m[e] = rec[j].m[e];
+          const V3 lo = m34_point(m, o);
+          const V3 ld = v3(m[0] * d.x + m[1] * d.y + m[2] * d.z, m[4] * d.x + m[5] * d.y + m[6] * d.z,
+                           m[8] * d.x + m[9] * d.y + m[10] * d.z);
+          sphere_test<true>(lo.x, lo.y, lo.z, ld.x, ld.y, ld.z, [&] { return rec[j].meta; }, h, n_disc);
+        } else {
+          quad_test<true>(rec + j, o, d, h);
+        }
+      } else {
+        double m[12];
+#pragma unroll
+        for (int e = 0; e < 12; ++e) m[e] = rec[j].m[e];
+        const V3 lo = m34_point(m, o);
+        const V3 ld = v3(m[0] * d.x + m[1] * d.y + m[2] * d.z, m[4] * d.x + m[5] * d.y + m[6] * d.z,
+                         m[8] * d.x + m[9] * d.y + m[10] * d.z);
+        double t[4];
+        int n = 0;
+        if (kind == 0) {  // sphere.rs:47-62 (sphere_test, sphere_adc)
+          const double a = ld.x * ld.x + ld.y * ld.y + ld.z * ld.z;
+          const double dt = ld.x * lo.x + ld.y * lo.y + ld.z * lo.z;
+          const double cc = lo.x * lo.x + lo.y * lo.y + lo.z * lo.z - 1.0;
+          const double disc = dt * dt - a * cc;
+          if (disc >= 0.0) {
+            ++n_disc;
+            const double q = sqrt(disc);
+            t[0] = (-dt - q) / a;
+            t[1] = (-dt + q) / a;
+            n = 2;
+          }
+        } else if (kind == 1) {  // plane.rs:53-60 (plane_test)
+          if (!(fabs(ld.y) < kEpsilon)) {
+            t[0] = -lo.y / ld.y;
+            n = 1;
+          }
+        } else {
+          n = quad_local_intersect(kind, rec[j].minimum, rec[j].maximum, rec[j].closed != 0, lo, ld, t);
+        }
+        const int k0 = (rec[j].meta >> 1) << kKeyShift;
+        for (int i = 0; i < n; ++i) {
+          if (t[i] < 0.0) {
+            ++n_neg;
+            if (t[i] > neg_t || (t[i] == neg_t && k0 + i > neg_k)) { neg_t = t[i]; neg_k = k0 + i; }
+          } else if (t[i] >= 0.0 && better(t[i], k0 + i, h.t, h.key)) {
+            h.t = t[i]; h.key = k0 + i; took = true;
+          }
+        }
+      }
+    }
+    if constexpr (!SHADOW) {
+      if (n_neg & 1) push_container(h, neg_t, neg_k);
+      if (took) h.hin = n_neg & 1;
+    }
+  }
+}
+// The gates alias_classes meets, without its tests (count_rest_gates).
+__device__ __forceinline__ void count_alias_gates(const DevScene& sc, V3 o, V3 d, GateSkips& sk) {
+  const cQuadRec rec = (cQuadRec)sc.alias_rec;
+  for (int j = 0; j < sc.n_alias_rec; ++j)
+    if (rec[j].gate && !group_gate(sc, rec[j].gate, o, d)) {
+      if (rec[j].kind == 0) ++sk.sph; else if (rec[j].kind == 1) ++sk.plane; else ++sk.other;
+    }
+}
+// After the whole trace of a radiance ray (hit_finish): prepare() asks whether the most recent
+// container IS the hit object by comparing object indices; with alias classes the question is
+// "the same class" (`position(|&el| el == i.object)`). When the hit object's class is that
+// container, the container's key is replaced by the hit's own: the same object as far as
+// prepare() can tell, and the same refractive index bit for bit. The stored hit (WfHit) and every
+// prepare() then stay what they are for a world without classes.
+__device__ __forceinline__ void alias_finish(const DevScene& sc, Hit& h) {
+  if (h.key >= 0 && h.hin && h.c1k >= 0) {
+    const int obj = h.key >> kKeyShift, c1 = h.c1k >> kKeyShift;
+    if (c1 != obj && sc.alias_of[c1] == sc.alias_of[obj]) h.c1k = h.key;
+  }
+}
+
 // The records outside the sphere BVH (general-transform spheres, planes,
 // cubes / cylinders / cones), tested exhaustively from global memory.
 // QUADS = false compiles the solids out (kernel variants for scenes without
@@ -510,7 +625,8 @@ __device__ __forceinline__ void csg_units(const DevScene& sc, const CsgUnit* uni
 // TRIS: the triangles too (the kernels of scenes without solids never meet one).
 // CSG: the Csg units too (csg_units): every unit, or on the fast path those outside the
 // units' hierarchy (fx_units; unit_trace walks the others).
-template <bool SHADOW, bool QUADS = true, bool FAST = false, bool TRIS = QUADS, bool CSG = false>
+// ALIAS (with CSG): the alias classes too (alias_classes), every member on either path.
+template <bool SHADOW, bool QUADS = true, bool FAST = false, bool TRIS = QUADS, bool CSG = false, bool ALIAS = false>
 __device__ __forceinline__ void trace_rest(const DevScene& sc, V3 o, V3 d, Hit& h, unsigned& n_disc,
                                            GateSkips* skips = nullptr) {
   cSphereGen sg = (cSphereGen)(FAST ? sc.fx_gen : sc.sph_gen);
@@ -563,14 +679,16 @@ __device__ __forceinline__ void trace_rest(const DevScene& sc, V3 o, V3 d, Hit& 
   if constexpr (CSG)
     csg_units<SHADOW, false>(sc, FAST ? sc.fx_units : sc.csg_units, FAST ? sc.n_fx_units : sc.n_csg_units, o, d, h, n_disc,
                              skips);
+  if constexpr (ALIAS) alias_classes<SHADOW>(sc, o, d, h, n_disc, skips);
 }
 
 // The group gates trace_rest<.., QUADS, true> meets, without its tests: a counted
 // launch's ray that is answered before trace_rest runs (shadow_trace's `first`)
 // still owes the reference's count of the shapes its groups kept out.
-template <bool QUADS, bool TRIS = QUADS, bool CSG = false>
+template <bool QUADS, bool TRIS = QUADS, bool CSG = false, bool ALIAS = false>
 __device__ __forceinline__ void count_rest_gates(const DevScene& sc, V3 o, V3 d, GateSkips& sk) {
   if (!sc.n_groups) return;
+  if constexpr (ALIAS) count_alias_gates(sc, o, d, sk);
   if constexpr (CSG) {
     Hit none;
     hit_init(none);
@@ -627,14 +745,16 @@ __device__ __forceinline__ void diag_test(cSphereDiag r, V3 o, V3 d, Hit& h, uns
 // loads): the batch entry points (rt_hit_batch, rt_is_shadowed_batch) and
 // the wavefront fallback when the trace image does not fit in LDS.
 // TRIS = false: a scene without solids or triangles (trace_rest). CSG: one with Csg units.
-template <bool SHADOW, bool TRIS = true, bool CSG = false>
+// ALIAS (with CSG): one with alias classes.
+template <bool SHADOW, bool TRIS = true, bool CSG = false, bool ALIAS = false>
 __device__ __forceinline__ void trace(const DevScene& sc, V3 o, V3 d, Hit& h, unsigned& n_disc,
                                       GateSkips* skips = nullptr) {
   hit_init(h);
   cSphereDiag sd = (cSphereDiag)sc.sph_diag;
   for (int j = 0; j < sc.n_diag; ++j) diag_test<SHADOW>(sd + j, o, d, h, n_disc);
-  trace_rest<SHADOW, true, false, TRIS, CSG>(sc, o, d, h, n_disc, skips);
+  trace_rest<SHADOW, true, false, TRIS, CSG, ALIAS>(sc, o, d, h, n_disc, skips);
   hit_finish(h);
+  if constexpr (ALIAS && !SHADOW) alias_finish(sc, h);
 }
 
 // --------------------------------------------------------------- shading

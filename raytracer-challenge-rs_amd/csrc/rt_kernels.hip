@@ -19,7 +19,8 @@ namespace rtamd {
 
 // rt_hit_batch: 24 doubles per ray (layout in include/rt_render.h).
 // CSG: the scene has Csg units (kernels of their own: the others keep their registers).
-template <bool CSG>
+// ALIAS (with CSG): it has alias classes (again kernels of their own).
+template <bool CSG, bool ALIAS = false>
 __device__ __forceinline__ void hit_body(const DevScene& sc, const double* rays, int n, double* out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -27,7 +28,7 @@ __device__ __forceinline__ void hit_body(const DevScene& sc, const double* rays,
   const V3 d = v3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
   Hit h;
   unsigned nd = 0;
-  trace<false, true, CSG>(sc, o, d, h, nd);
+  trace<false, true, CSG, ALIAS>(sc, o, d, h, nd);
   double* r = out + (size_t)i * 24;
   for (int k = 0; k < 24; ++k) r[k] = 0.0;
   r[0] = -1.0;
@@ -51,9 +52,12 @@ __global__ __launch_bounds__(256) void hit_kernel(DevScene sc, const double* ray
 __global__ __launch_bounds__(256) void hit_kernel_csg(DevScene sc, const double* rays, int n, double* out) {
   hit_body<true>(sc, rays, n, out);
 }
+__global__ __launch_bounds__(256) void hit_kernel_alias(DevScene sc, const double* rays, int n, double* out) {
+  hit_body<true, true>(sc, rays, n, out);
+}
 
 // rt_is_shadowed_batch: World::is_shadowed for each point against one light.
-template <bool CSG>
+template <bool CSG, bool ALIAS = false>
 __device__ __forceinline__ void shadow_body(const DevScene& sc, const double* pts, int n, int light, uint8_t* out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -64,7 +68,7 @@ __device__ __forceinline__ void shadow_body(const DevScene& sc, const double* pt
   const V3 d = vnormalize(v);
   Hit h;
   unsigned nd = 0;
-  trace<true, true, CSG>(sc, p, d, h, nd);
+  trace<true, true, CSG, ALIAS>(sc, p, d, h, nd);
   out[i] = (h.key >= 0 && h.t < distance) ? 1 : 0;
 }
 __global__ __launch_bounds__(256) void shadow_kernel(DevScene sc, const double* pts, int n, int light,
@@ -75,16 +79,23 @@ __global__ __launch_bounds__(256) void shadow_kernel_csg(DevScene sc, const doub
                                                          uint8_t* out) {
   shadow_body<true>(sc, pts, n, light, out);
 }
+__global__ __launch_bounds__(256) void shadow_kernel_alias(DevScene sc, const double* pts, int n, int light,
+                                                           uint8_t* out) {
+  shadow_body<true, true>(sc, pts, n, light, out);
+}
 
 hipError_t launch_hit(const DevScene& sc, const double* d_rays, int n, double* d_out, hipStream_t s) {
-  if (sc.n_csg_units > 0) hipLaunchKernelGGL(hit_kernel_csg, dim3((n + 255) / 256), dim3(256), 0, s, sc, d_rays, n, d_out);
+  if (sc.n_alias_rec > 0) hipLaunchKernelGGL(hit_kernel_alias, dim3((n + 255) / 256), dim3(256), 0, s, sc, d_rays, n, d_out);
+  else if (sc.n_csg_units > 0) hipLaunchKernelGGL(hit_kernel_csg, dim3((n + 255) / 256), dim3(256), 0, s, sc, d_rays, n, d_out);
   else hipLaunchKernelGGL(hit_kernel, dim3((n + 255) / 256), dim3(256), 0, s, sc, d_rays, n, d_out);
   return hipGetLastError();
 }
 
 hipError_t launch_shadow(const DevScene& sc, const double* d_pts, int n, int light, uint8_t* d_out,
                          hipStream_t s) {
-  if (sc.n_csg_units > 0)
+  if (sc.n_alias_rec > 0)
+    hipLaunchKernelGGL(shadow_kernel_alias, dim3((n + 255) / 256), dim3(256), 0, s, sc, d_pts, n, light, d_out);
+  else if (sc.n_csg_units > 0)
     hipLaunchKernelGGL(shadow_kernel_csg, dim3((n + 255) / 256), dim3(256), 0, s, sc, d_pts, n, light, d_out);
   else hipLaunchKernelGGL(shadow_kernel, dim3((n + 255) / 256), dim3(256), 0, s, sc, d_pts, n, light, d_out);
   return hipGetLastError();

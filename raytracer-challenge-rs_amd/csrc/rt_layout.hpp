@@ -122,6 +122,16 @@ struct alignas(16) CsgUnit {
   int32_t first, n, gate, counts;
 };
 static_assert(sizeof(QuadRec) == 128, "QuadRec must stay 128 B");
+// ---- Alias classes (rt_scene_create_aliased): shapes the caller's structural `==` holds
+// between, every two of a class (exact and near duplicates). In the `containers` walk of
+// prepare_computations (intersection.rs:63-90) a class is ONE entry: `contains` and `position`
+// find whichever member is there. Its members (kinds 0-4, top level or inside groups) live only
+// in DevScene::alias_rec, general records with their group gate as the leaves under a Csg are
+// (kind 0 sphere, 1 plane, 2-4 solids), grouped by class: records [first, first + n). They keep
+// their object index (`meta`), so the closest hit, shading, shadows and the tie order are theirs.
+struct alignas(8) AliasClass {
+  int32_t first, n;
+};
 // The rays the unit hierarchy's padding is sized for (rt_bvh.cpp csg_unit_box, rt_trace.hpp
 // unit_trace): finite, |d|_inf at least kUnitDirMin (a unit vector's is 0.577), from origins
 // with |o|_inf at most kUnitOriginMax (a cube leaf's box grows with it: EPSILON times the
@@ -389,6 +399,14 @@ struct DevScene {
   const CsgUnit* urec;
   const CsgUnit* fx_units;
   int32_t n_ubvh, n_urec, n_fx_units, ubvh_depth;
+  // Alias classes (rt_scene_create_aliased; alias_classes): the members' records grouped by
+  // class, the classes, and per object the least object index of its class (its own index when
+  // it is in none: alias_finish). The members by counter class, as the Csg leaves.
+  const OtherRec* alias_rec;
+  const AliasClass* alias_cls;
+  const int32_t* alias_of;
+  int32_t n_alias_rec, n_alias_cls;
+  int32_t n_alias_sph, n_alias_planes, n_alias_other, pad_alias;
 };
 
 constexpr int32_t kOwnOutside = 0x40000000, kOwnIndex = 0x3FFFFFFF;  // DevScene::obj_diag

@@ -4,6 +4,7 @@
 // (rt_bvh.cpp), the light buffer, and one upload to the scene's device.
 #include <functional>
 
+#include "rt_alias.hpp"
 #include "rt_api_internal.hpp"
 #include "rt_csg.hpp"
 #include "rt_wf_plan.hpp"
@@ -17,132 +18,24 @@ bool is_diag_inverse(const double* inv) {
          inv[9] == 0.0;
 }
 
-bool m16_eq(const double* a, const double* b) {
-  for (int i = 0; i < 16; ++i)
-    if (!rt::equal(a[i], b[i])) return false;
-  return true;
-}
-bool c3_eq(const double* a, const double* b) {
-  return rt::equal(a[0], b[0]) && rt::equal(a[1], b[1]) && rt::equal(a[2], b[2]);
-}
-
-// Necessary condition for the reference's structural `Shape` equality
-// (derived PartialEq of BaseShape, geometry/mod.rs:12; Material, material.rs:10;
-// Pattern, pattern/mod.rs:17). The bounding box is left out, so this is a
-// SUPERSET of the reference relation: "no pair passes" certifies that the
-// containers walk never sees two structurally-equal objects.
-// `ta`, `tb`: the vertices of a Triangle / SmoothTriangle (null for the other kinds): the derived
-// PartialEq compares p1..p3, and n1..n3 of the smooth kind, through Point's and Vector's `equal()`
-// (triangle.rs:12, smooth_triangle.rs:12); e1, e2 and normal follow from the points.
-bool may_be_equal(const rt_shape_desc& a, const rt_shape_desc& b, const rt_triangle_desc* ta = nullptr,
-                  const rt_triangle_desc* tb = nullptr) {
-  if (a.kind != b.kind || (a.casts_shadow != 0) != (b.casts_shadow != 0)) return false;
-  if (ta && tb) {  // first: the triangles of a mesh share everything else
-    if (!(c3_eq(ta->p1, tb->p1) && c3_eq(ta->p2, tb->p2) && c3_eq(ta->p3, tb->p3))) return false;
-    if (a.kind == RT_SHAPE_SMOOTH_TRIANGLE && !(c3_eq(ta->n1, tb->n1) && c3_eq(ta->n2, tb->n2) && c3_eq(ta->n3, tb->n3)))
-      return false;
-  }
-  if (!m16_eq(a.transform, b.transform) || !m16_eq(a.inverse, b.inverse)) return false;
-  if (!c3_eq(a.color, b.color)) return false;
-  if (!(a.ambient == b.ambient && a.diffuse == b.diffuse && a.specular == b.specular &&
-        a.shininess == b.shininess && a.reflective == b.reflective &&
-        a.transparency == b.transparency && a.refractive_index == b.refractive_index))
-    return false;
-  if ((a.kind == RT_SHAPE_CYLINDER || a.kind == RT_SHAPE_CONE) &&
-      !(a.minimum == b.minimum && a.maximum == b.maximum && (a.closed != 0) == (b.closed != 0)))
-    return false;
-  if (a.pattern_kind != b.pattern_kind) return false;
-  if (a.pattern_kind != RT_PATTERN_NONE) {
-    if (!m16_eq(a.pattern_transform, b.pattern_transform) ||
-        !m16_eq(a.pattern_inverse, b.pattern_inverse))
-      return false;
-    if (a.pattern_kind != RT_PATTERN_TEST && !(c3_eq(a.pattern_a, b.pattern_a) && c3_eq(a.pattern_b, b.pattern_b)))
-      return false;
-  }
-  return true;
-}
+using rtalias::may_be_equal;
 
 // `tri_of[i]`: shape i's vertices (null: not a triangle; `tri_of` empty: no triangles at all).
 int find_duplicate(const rt_shape_desc* s, size_t n, const std::vector<const rt_triangle_desc*>& tri_of, size_t* ia,
                    size_t* ib) {
-  // Equal shapes have |translation-x difference| < EPSILON: sweep a sorted key. The triangles of
-  // a mesh share their transform, so their key adds p1: x + c1 y + c2 z with incommensurable
-  // weights keeps the vertices of a regular grid apart; equal triangles' keys differ by less
-  // than (2 + c1 + c2) EPSILON (and the rounding of the key itself, the relative term).
-  constexpr double c1 = 0.7548776662466927, c2 = 0.5698402909980532;
-  const bool tris = !tri_of.empty();
-  std::vector<std::pair<double, size_t>> key(n);  // (key, shape), sorted by value: no indirection in the sort
-  for (size_t i = 0; i < n; ++i) {
-    double k = s[i].transform[3];
-    if (tris && tri_of[i]) k += tri_of[i]->p1[0] + c1 * tri_of[i]->p1[1] + c2 * tri_of[i]->p1[2];
-    key[i] = {std::isfinite(k) ? k : INFINITY, i};  // (a non-finite coordinate equals nothing)
-  }
-  const double window = tris ? (2.0 + c1 + c2) * rt::EPSILON : rt::EPSILON;
-  std::sort(key.begin(), key.end());
-  std::vector<size_t> idx(n);
-  for (size_t i = 0; i < n; ++i) idx[i] = key[i].second;
-  for (size_t p = 0; p < n; ++p)
-    for (size_t q = p + 1;
-         q < n && key[q].first - key[p].first < window + (tris ? 1e-13 * (std::fabs(key[q].first) + std::fabs(key[p].first)) : 0.0);
-         ++q)
-      if (may_be_equal(s[idx[p]], s[idx[q]], tris ? tri_of[idx[p]] : nullptr, tris ? tri_of[idx[q]] : nullptr)) {
-        *ia = std::min(idx[p], idx[q]);
-        *ib = std::max(idx[p], idx[q]);
-        return 1;
-      }
-  return 0;
+  return rtalias::sweep_candidates(s, n, tri_of, [&](size_t a, size_t b) {
+    *ia = a;
+    *ib = b;
+    return true;
+  }) ? 1 : 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int rt_scene_create(const rt_shape_desc* shapes, size_t n_shapes, const rt_light_desc* lights,
-                    size_t n_lights, int device, rt_scene** out) {
-  return guarded([&]() -> int {
-  return rt_scene_create_groups(shapes, n_shapes, nullptr, nullptr, 0, lights, n_lights, device, out);
-  });
-}
-
-int rt_scene_create_groups(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* shape_group,
-                           const rt_group_desc* groups, size_t n_groups, const rt_light_desc* lights,
-                           size_t n_lights, int device, rt_scene** out) {
-  return rt_scene_create_mesh(shapes, n_shapes, shape_group, groups, n_groups, nullptr, 0, lights, n_lights, device, out);
-}
-
-// rt_scene_create_groups / _mesh: the tree whose nodes are all Groups.
-int rt_scene_create_mesh(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* shape_group,
-                         const rt_group_desc* groups, size_t n_groups, const rt_triangle_desc* tri_descs, size_t n_tris,
-                         const rt_light_desc* lights, size_t n_lights, int device, rt_scene** out) {
-  return guarded([&]() -> int {
-  if (!out || (n_shapes && !shapes) || (n_lights && !lights) || (n_groups && (!groups || !shape_group)) ||
-      (n_tris && !tri_descs))
-    return fail(RT_ERR_INVALID_ARGUMENT, "null pointer");
-  *out = nullptr;
-  if (n_groups > (size_t)(1u << 24)) return fail(RT_ERR_INVALID_ARGUMENT, "too many groups");
-  for (size_t g = 0; g < n_groups; ++g)
-    if (groups[g].parent < -1 || groups[g].parent >= (int32_t)g)
-      return fail(RT_ERR_INVALID_ARGUMENT, "group " + std::to_string(g) + ": its parent must be -1 or an earlier group");
-  for (size_t i = 0; n_groups && i < n_shapes; ++i)
-    if (shape_group[i] < -1 || (int64_t)shape_group[i] >= (int64_t)n_groups)
-      return fail(RT_ERR_INVALID_ARGUMENT, "shape " + std::to_string(i) + ": bad group index");
-  std::vector<rt_node_desc> nodes(n_groups);
-  for (size_t g = 0; g < n_groups; ++g) {
-    nodes[g] = rt_node_desc{};
-    nodes[g].kind = RT_NODE_GROUP;
-    nodes[g].parent = groups[g].parent;
-    for (int c = 0; c < 3; ++c) { nodes[g].min[c] = groups[g].min[c]; nodes[g].max[c] = groups[g].max[c]; }
-  }
-  return rt_scene_create_tree(shapes, n_shapes, shape_group, nullptr, nodes.data(), n_groups, tri_descs, n_tris, lights,
-                              n_lights, device, out);
-  });
-}
-
-int rt_scene_create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* shape_node,
-                         const int32_t* shape_side, const rt_node_desc* nodes, size_t n_nodes,
-                         const rt_triangle_desc* tri_descs, size_t n_tris, const rt_light_desc* lights, size_t n_lights,
-                         int device, rt_scene** out) {
-  return guarded([&]() -> int {
+// rt_scene_create_tree (aliased = false: two shapes that may be structurally equal are refused)
+// and rt_scene_create_aliased (the caller's equal pairs: alias classes).
+int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* shape_node, const int32_t* shape_side,
+                const rt_node_desc* nodes, size_t n_nodes, const rt_triangle_desc* tri_descs, size_t n_tris,
+                const rt_light_desc* lights, size_t n_lights, bool aliased, const int32_t* equal_pairs, size_t n_pairs,
+                int device, rt_scene** out) {
   if (!out || (n_shapes && !shapes) || (n_lights && !lights) || (n_nodes && (!nodes || !shape_node)) ||
       (n_tris && !tri_descs))
     return fail(RT_ERR_INVALID_ARGUMENT, "null pointer");
@@ -222,9 +115,46 @@ int rt_scene_create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int
                                                std::to_string(j) + " triangles");
   }
   size_t da, db;
-  if (find_duplicate(shapes, n_shapes, tri_of, &da, &db))
+  if (!aliased && find_duplicate(shapes, n_shapes, tri_of, &da, &db))
     return fail(RT_ERR_DUPLICATE_SHAPES, "shapes " + std::to_string(da) + " and " + std::to_string(db) +
                                              " may be structurally equal (containers walk, intersection.rs:63-90)");
+  // ---- the caller's equal pairs: alias classes (rt_layout.hpp AliasClass). No pair of
+  // primitives is looked for on this path: an unlisted pair is distinct. (Triangles: below.)
+  std::vector<int32_t> class_of;                 // per shape: its alias class, -1 none
+  std::vector<std::vector<int32_t>> alias_cls;   // per class: its members, ascending
+  if (aliased) {
+    for (size_t p = 0; p < n_pairs; ++p) {
+      const int64_t a = equal_pairs[2 * p], b = equal_pairs[2 * p + 1];
+      const std::string which = "equal pair " + std::to_string(p) + " (" + std::to_string(a) + ", " + std::to_string(b) + ")";
+      if (a < 0 || b >= (int64_t)n_shapes || a >= b)
+        return fail(RT_ERR_INVALID_ARGUMENT, which + ": needs 0 <= i < j < n_shapes");
+      if (p > 0 && !(equal_pairs[2 * p - 2] < a || (equal_pairs[2 * p - 2] == a && equal_pairs[2 * p - 1] < b)))
+        return fail(RT_ERR_INVALID_ARGUMENT, which + ": the pairs must be sorted by (i, j), without repeats");
+      if (!may_be_equal(shapes[a], shapes[b], n_tris ? tri_of[(size_t)a] : nullptr, n_tris ? tri_of[(size_t)b] : nullptr))
+        return fail(RT_ERR_INVALID_ARGUMENT, which + ": the two descriptors differ in a field structural equality compares");
+    }
+    for (size_t p = 0; p < n_pairs; ++p) {
+      const int32_t a = equal_pairs[2 * p], b = equal_pairs[2 * p + 1];
+      const std::string which = "shapes " + std::to_string(a) + " and " + std::to_string(b) + " are structurally equal";
+      if (shapes[a].kind >= RT_SHAPE_TRIANGLE)
+        return fail(RT_ERR_DUPLICATE_SHAPES, which + ": aliased triangles are not supported");
+      if (unit_of[(size_t)a] >= 0 || unit_of[(size_t)b] >= 0)
+        return fail(RT_ERR_DUPLICATE_SHAPES, which + ": an aliased primitive under a Csg is not supported");
+    }
+    // The triangles keep the other entry points' refusal, listed or not: no yardstick restates
+    // structural equality for them, so two that may be equal are never rendered as distinct.
+    if (n_tris && rtalias::sweep_candidates(shapes, n_shapes, tri_of, [&](size_t a, size_t b) { da = a; db = b; return true; },
+                                            rtalias::kSweepTriangles))
+      return fail(RT_ERR_DUPLICATE_SHAPES, "shapes " + std::to_string(da) + " and " + std::to_string(db) +
+                                               " may be structurally equal: aliased triangles are not supported");
+    int32_t ba = -1, bb = -1;
+    if (!rtalias::split_classes(n_shapes, equal_pairs, n_pairs, &class_of, &alias_cls, &ba, &bb))
+      return fail(RT_ERR_DUPLICATE_SHAPES,
+                  "shapes " + std::to_string(ba) + " and " + std::to_string(bb) +
+                      " are not equal but are linked by a chain of equal pairs: structural equality is not transitive"
+                      " there, and only complete components (alias classes) are supported");
+  }
+  if (class_of.empty()) class_of.assign(n_shapes, -1);
 
   int ndev = rt_device_count();
   if (ndev <= 0) return fail(RT_ERR_NO_DEVICE, "no HIP device available (no CPU fallback)");
@@ -241,11 +171,39 @@ int rt_scene_create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int
   std::vector<OtherRec> csg_leaves;  // the leaves under Csg units live only here
   std::vector<int32_t> leaf_of(n_shapes, -1);
   int32_t n_csg_kind[3] = {0, 0, 0};  // by counter class: spheres, planes, others
+  // the alias classes' members, class by class (a class's members in object order); they enter
+  // no other record list, so no sphere image, LDS plan, light buffer, own-sphere shadow rule or
+  // hierarchy knows them: every ray tests every member behind its group gate (alias_classes)
+  std::vector<OtherRec> alias_rec;
+  std::vector<AliasClass> alias_tab;
+  std::vector<int32_t> alias_of;  // (only a world with a class has the table)
+  int32_t n_alias_kind[3] = {0, 0, 0};
+  if (!alias_cls.empty()) {
+    alias_of.assign(n_shapes + 1, 0);
+    for (size_t i = 0; i < n_shapes; ++i) alias_of[i] = class_of[i] >= 0 ? alias_cls[(size_t)class_of[i]][0] : (int32_t)i;
+  }
+  for (const std::vector<int32_t>& members : alias_cls) {
+    alias_tab.push_back(AliasClass{(int32_t)alias_rec.size(), (int32_t)members.size()});
+    for (const int32_t i : members) {
+      const rt_shape_desc& d = shapes[i];
+      OtherRec r{};
+      for (int e = 0; e < 12; ++e) r.m[e] = d.inverse[e];
+      r.minimum = d.minimum;
+      r.maximum = d.maximum;
+      r.kind = d.kind;
+      r.closed = d.closed ? 1 : 0;
+      r.meta = (int32_t)(((int64_t)i << 1) | (d.casts_shadow ? 1 : 0));
+      r.gate = gate_of((size_t)i);
+      alias_rec.push_back(r);
+    }
+  }
   for (size_t i = 0; i < n_shapes; ++i) {
     const rt_shape_desc& d = shapes[i];
     const int64_t meta = ((int64_t)i << 1) | (d.casts_shadow ? 1 : 0);
     const int32_t gate = gate_of(i);  // shapes inside groups: general records with their group gate
-    if (unit_of[i] >= 0) {  // its gates are the unit's program's (csg_units)
+    if (class_of[i] >= 0) {  // a member of an alias class: only in its class's records (below)
+      ++n_alias_kind[d.kind == RT_SHAPE_SPHERE ? 0 : d.kind == RT_SHAPE_PLANE ? 1 : 2];
+    } else if (unit_of[i] >= 0) {  // its gates are the unit's program's (csg_units)
       OtherRec r{};
       for (int e = 0; e < 12; ++e) r.m[e] = d.inverse[e];
       r.minimum = d.minimum;
@@ -581,7 +539,10 @@ int rt_scene_create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int
   const size_t o_ub = align(o_cl + (csg_leaves.size() + 1) * sizeof(OtherRec));
   const size_t o_ur = align(o_ub + (ubvh.size() + 1) * sizeof(BvhNode));
   const size_t o_ux = align(o_ur + (urec.size() + 1) * sizeof(CsgUnit));
-  const size_t total = align(o_ux + (fx_units.size() + 1) * sizeof(CsgUnit)) + 256;
+  const size_t o_ar = align(o_ux + (fx_units.size() + 1) * sizeof(CsgUnit));
+  const size_t o_ac = align(o_ar + (alias_rec.size() + 1) * sizeof(OtherRec));
+  const size_t o_ao = align(o_ac + (alias_tab.size() + 1) * sizeof(AliasClass));
+  const size_t total = align(o_ao + (alias_of.size() + 1) * sizeof(int32_t)) + 256;
   std::vector<unsigned char> host(total, 0);
   if (!diag.empty()) std::memcpy(&host[o_diag], diag.data(), diag.size() * sizeof(SphereDiag));
   if (!gen.empty()) std::memcpy(&host[o_gen], gen.data(), gen.size() * sizeof(SphereGen));
@@ -637,6 +598,9 @@ int rt_scene_create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int
   if (!ubvh.empty()) std::memcpy(&host[o_ub], ubvh.data(), ubvh.size() * sizeof(BvhNode));
   if (!urec.empty()) std::memcpy(&host[o_ur], urec.data(), urec.size() * sizeof(CsgUnit));
   if (!fx_units.empty()) std::memcpy(&host[o_ux], fx_units.data(), fx_units.size() * sizeof(CsgUnit));
+  if (!alias_rec.empty()) std::memcpy(&host[o_ar], alias_rec.data(), alias_rec.size() * sizeof(OtherRec));
+  if (!alias_tab.empty()) std::memcpy(&host[o_ac], alias_tab.data(), alias_tab.size() * sizeof(AliasClass));
+  if (!alias_of.empty()) std::memcpy(&host[o_ao], alias_of.data(), alias_of.size() * sizeof(int32_t));
   if (!lb.cells.empty()) {
     std::memcpy(&host[o_lc], lb.cells.data(), lb.cells.size() * sizeof(LbCell));
     if (!lb.ov.empty()) std::memcpy(&host[o_lv], lb.ov.data(), lb.ov.size() * sizeof(uint16_t));
@@ -737,6 +701,14 @@ int rt_scene_create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int
   s->dev.n_urec = (int32_t)urec.size();
   s->dev.n_fx_units = (int32_t)fx_units.size();
   s->dev.ubvh_depth = ubvh_depth;
+  s->dev.alias_rec = (const OtherRec*)(b + o_ar);
+  s->dev.alias_cls = (const AliasClass*)(b + o_ac);
+  s->dev.alias_of = alias_of.empty() ? nullptr : (const int32_t*)(b + o_ao);
+  s->dev.n_alias_rec = (int32_t)alias_rec.size();
+  s->dev.n_alias_cls = (int32_t)alias_tab.size();
+  s->dev.n_alias_sph = n_alias_kind[0];
+  s->dev.n_alias_planes = n_alias_kind[1];
+  s->dev.n_alias_other = n_alias_kind[2];
   s->dev.n_diag = (int32_t)diag.size();
   s->dev.n_gen = (int32_t)gen.size();
   s->dev.n_planes = (int32_t)planes.size();
@@ -747,6 +719,88 @@ int rt_scene_create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int
   s->n_lights = (int)n_lights;
   *out = s;
   return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_scene_create(const rt_shape_desc* shapes, size_t n_shapes, const rt_light_desc* lights,
+                    size_t n_lights, int device, rt_scene** out) {
+  return guarded([&]() -> int {
+  return rt_scene_create_groups(shapes, n_shapes, nullptr, nullptr, 0, lights, n_lights, device, out);
+  });
+}
+
+int rt_scene_create_groups(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* shape_group,
+                           const rt_group_desc* groups, size_t n_groups, const rt_light_desc* lights,
+                           size_t n_lights, int device, rt_scene** out) {
+  return rt_scene_create_mesh(shapes, n_shapes, shape_group, groups, n_groups, nullptr, 0, lights, n_lights, device, out);
+}
+
+// rt_scene_create_groups / _mesh: the tree whose nodes are all Groups.
+int rt_scene_create_mesh(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* shape_group,
+                         const rt_group_desc* groups, size_t n_groups, const rt_triangle_desc* tri_descs, size_t n_tris,
+                         const rt_light_desc* lights, size_t n_lights, int device, rt_scene** out) {
+  return guarded([&]() -> int {
+  if (!out || (n_shapes && !shapes) || (n_lights && !lights) || (n_groups && (!groups || !shape_group)) ||
+      (n_tris && !tri_descs))
+    return fail(RT_ERR_INVALID_ARGUMENT, "null pointer");
+  *out = nullptr;
+  if (n_groups > (size_t)(1u << 24)) return fail(RT_ERR_INVALID_ARGUMENT, "too many groups");
+  for (size_t g = 0; g < n_groups; ++g)
+    if (groups[g].parent < -1 || groups[g].parent >= (int32_t)g)
+      return fail(RT_ERR_INVALID_ARGUMENT, "group " + std::to_string(g) + ": its parent must be -1 or an earlier group");
+  for (size_t i = 0; n_groups && i < n_shapes; ++i)
+    if (shape_group[i] < -1 || (int64_t)shape_group[i] >= (int64_t)n_groups)
+      return fail(RT_ERR_INVALID_ARGUMENT, "shape " + std::to_string(i) + ": bad group index");
+  std::vector<rt_node_desc> nodes(n_groups);
+  for (size_t g = 0; g < n_groups; ++g) {
+    nodes[g] = rt_node_desc{};
+    nodes[g].kind = RT_NODE_GROUP;
+    nodes[g].parent = groups[g].parent;
+    for (int c = 0; c < 3; ++c) { nodes[g].min[c] = groups[g].min[c]; nodes[g].max[c] = groups[g].max[c]; }
+  }
+  return rt_scene_create_tree(shapes, n_shapes, shape_group, nullptr, nodes.data(), n_groups, tri_descs, n_tris, lights,
+                              n_lights, device, out);
+  });
+}
+
+int rt_scene_create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* shape_node,
+                         const int32_t* shape_side, const rt_node_desc* nodes, size_t n_nodes,
+                         const rt_triangle_desc* tri_descs, size_t n_tris, const rt_light_desc* lights, size_t n_lights,
+                         int device, rt_scene** out) {
+  return guarded([&]() -> int {
+    return create_tree(shapes, n_shapes, shape_node, shape_side, nodes, n_nodes, tri_descs, n_tris, lights, n_lights,
+                       false, nullptr, 0, device, out);
+  });
+}
+
+int rt_scene_create_aliased(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* shape_node,
+                            const int32_t* shape_side, const rt_node_desc* nodes, size_t n_nodes,
+                            const rt_triangle_desc* tri_descs, size_t n_tris, const rt_light_desc* lights,
+                            size_t n_lights, const int32_t* equal_pairs, size_t n_pairs, int device, rt_scene** out) {
+  return guarded([&]() -> int {
+    if (n_pairs && !equal_pairs) return fail(RT_ERR_INVALID_ARGUMENT, "null pointer");
+    return create_tree(shapes, n_shapes, shape_node, shape_side, nodes, n_nodes, tri_descs, n_tris, lights, n_lights,
+                       true, equal_pairs, n_pairs, device, out);
+  });
+}
+
+int rt_shapes_equal_pairs(const rt_shape_desc* shapes, size_t n_shapes, int32_t* out_pairs, size_t cap,
+                          size_t* n_pairs) {
+  return guarded([&]() -> int {
+    if (!n_pairs || (n_shapes && !shapes) || (cap && !out_pairs)) return fail(RT_ERR_INVALID_ARGUMENT, "null pointer");
+    if (n_shapes > (size_t)(1u << 29)) return fail(RT_ERR_INVALID_ARGUMENT, "too many shapes");
+    const std::vector<std::pair<int32_t, int32_t>> pairs = rtalias::equal_pairs(shapes, n_shapes);
+    *n_pairs = pairs.size();
+    for (size_t p = 0; p < pairs.size() && p < cap; ++p) {
+      out_pairs[2 * p] = pairs[p].first;
+      out_pairs[2 * p + 1] = pairs[p].second;
+    }
+    if (pairs.size() > cap)
+      return fail(RT_ERR_BUFFER_TOO_SMALL, "the shapes hold " + std::to_string(pairs.size()) + " equal pairs");
+    return RT_OK;
   });
 }
 

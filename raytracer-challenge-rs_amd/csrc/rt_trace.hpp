@@ -1232,7 +1232,8 @@ __device__ __forceinline__ void lb_walk(const DevScene& sc, SD sd, const float* 
 // the other hierarchy's, count_hier_gates).
 // TRIS: the scene has triangles (trace_rest's loop over those outside the hierarchy, tri_trace).
 // CSG: the scene has Csg units (trace_rest's csg_units over those outside their hierarchy, unit_trace).
-template <bool QUADS, bool TALLY = false, bool TRIS = false, bool CSG = false, typename Image>
+// ALIAS: the scene has alias classes (trace_rest's alias_classes: ordinary blockers here).
+template <bool QUADS, bool TALLY = false, bool TRIS = false, bool CSG = false, bool ALIAS = false, typename Image>
 __device__ __forceinline__ bool shadow_trace(const DevScene& sc, unsigned use_lb, const Image& img, unsigned l,
                                              V3 o, V3 d, double dist, unsigned& n_disc, unsigned& n_tests,
                                              unsigned& n_boxes, GateSkips* skips = nullptr, int first = -1,
@@ -1244,12 +1245,12 @@ __device__ __forceinline__ bool shadow_trace(const DevScene& sc, unsigned use_lb
     ++n_tests;
     if (h.key >= 0 && h.t < dist) {
       if constexpr (TALLY) {
-        if (skips) count_rest_gates<QUADS, TRIS, CSG>(sc, o, d, *skips);
+        if (skips) count_rest_gates<QUADS, TRIS, CSG, ALIAS>(sc, o, d, *skips);
       }
       return true;
     }
   }
-  trace_rest<true, QUADS, true, TRIS, CSG>(sc, o, d, h, n_disc, skips);
+  trace_rest<true, QUADS, true, TRIS, CSG, ALIAS>(sc, o, d, h, n_disc, skips);
   if constexpr (QUADS) {
     other_trace<true>(sc, o, d, dist, h, n_disc, n_tests, n_boxes);
     line_trace<true>(sc, o, d, dist, h, n_tests, n_boxes);

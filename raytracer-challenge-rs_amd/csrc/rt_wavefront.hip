@@ -325,32 +325,33 @@ static hipError_t launch_timed(K kern, int block, size_t dyn, unsigned n, hipStr
 
 // ---- the exhaustive pipeline (counted launches: the reference's every-shape loop)
 // CSG (with QUADS): the scene has Csg units (kernels of their own, as the fused ones).
-template <bool QUADS, bool CSG = false>
+// ALIAS (with CSG): it has alias classes (again kernels of their own).
+template <bool QUADS, bool CSG = false, bool ALIAS = false>
 static hipError_t launch_closest_exh(const DevScene& sc, const DevCamera& cam, const WfArgs& a, bool primary,
                                      bool lds_ok, unsigned n, hipStream_t stream, const WfTuning& tn) {
   const int tb = trace_block(n, tn.adaptive_block);
   if (primary)
-    return launch_timed(wf_trace_closest<true, true, QUADS, 8, CSG>, tb, wf_lds_bytes(sc.n_diag, sc.n_gen, sc.n_planes, true),
+    return launch_timed(wf_trace_closest<true, true, QUADS, 8, CSG, ALIAS>, tb, wf_lds_bytes(sc.n_diag, sc.n_gen, sc.n_planes, true),
                         n, stream, sc, cam, a);
   if (lds_ok)
-    return launch_timed(wf_trace_closest<true, false, QUADS, 8, CSG>, tb,
+    return launch_timed(wf_trace_closest<true, false, QUADS, 8, CSG, ALIAS>, tb,
                         wf_lds_bytes(sc.n_diag, sc.n_gen, sc.n_planes, false), n, stream, sc, cam, a);
-  return launch_timed(wf_trace_closest<false, false, QUADS, 8, CSG>, tb, 0, n, stream, sc, cam, a);
+  return launch_timed(wf_trace_closest<false, false, QUADS, 8, CSG, ALIAS>, tb, 0, n, stream, sc, cam, a);
 }
-template <bool QUADS, bool CSG = false>
+template <bool QUADS, bool CSG = false, bool ALIAS = false>
 static hipError_t launch_shadow_exh(const DevScene& sc, const WfArgs& a, bool lds_ok, hipStream_t stream,
                                     const WfTuning& tn) {
   const int tb = trace_block(a.n_shadow, tn.adaptive_block);
   if (lds_ok)
-    return launch_timed(wf_trace_shadow<true, QUADS, 8, CSG>, tb, wf_lds_bytes(sc.n_diag, sc.n_gen, sc.n_planes, false),
+    return launch_timed(wf_trace_shadow<true, QUADS, 8, CSG, ALIAS>, tb, wf_lds_bytes(sc.n_diag, sc.n_gen, sc.n_planes, false),
                         a.n_shadow, stream, sc, a);
-  return launch_timed(wf_trace_shadow<false, QUADS, 8, CSG>, tb, 0, a.n_shadow, stream, sc, a);
+  return launch_timed(wf_trace_shadow<false, QUADS, 8, CSG, ALIAS>, tb, 0, a.n_shadow, stream, sc, a);
 }
 
 // ---- the fast path: one fused launch per generation over the image wf_plan_image chooses
 // (rt_wf_plan.hpp); `ran` receives the plan. The global-memory images' launches live in their
 // own code object (rt_wavefront_glb.o).
-template <bool QUADS, bool TALLY, bool TRIS = false, bool CSG = false>
+template <bool QUADS, bool TALLY, bool TRIS = false, bool CSG = false, bool ALIAS = false>
 static hipError_t launch_fused_q(const DevScene& sc, const DevCamera& cam, WfArgs a, bool primary, unsigned n,
                                  hipStream_t stream, const WfTuning& tn, WfImagePlan* ran) {
   // (spread: the whole grid, whatever n; the kernel deals the chunks over every block)
@@ -360,7 +361,7 @@ static hipError_t launch_fused_q(const DevScene& sc, const DevCamera& cam, WfArg
   a.lds_flags = plan.lds_flags;
   a.n_top = plan.n_top;
   const bool cam_rays = a.g == 0 && a.camera_mode;  // only generation 0 of a camera render reads camera rays
-#define RT_LDS(P, L, C) launch_timed(wf_trace_fused<P, QUADS, L, TALLY, C, TRIS, CSG>, tb, plan.dyn, n, stream, sc, cam, a)
+#define RT_LDS(P, L, C) launch_timed(wf_trace_fused<P, QUADS, L, TALLY, C, TRIS, CSG, ALIAS>, tb, plan.dyn, n, stream, sc, cam, a)
   switch (plan.lane) {
     case kLaneWave: return RT_LDS(true, kLaneWave, true);
     case kLaneWideLds: return cam_rays ? RT_LDS(false, kLaneWideLds, true) : RT_LDS(false, kLaneWideLds, false);
@@ -368,12 +369,15 @@ static hipError_t launch_fused_q(const DevScene& sc, const DevCamera& cam, WfArg
   }
 #undef RT_LDS
   if (t_ev_start) ++t_ev_used;
-  return wf_launch_global(plan.lane, QUADS, TRIS, CSG, TALLY, cam_rays, sc, cam, a, plan.dyn, n, stream, tb, t_ev_start, t_ev_stop);
+  return wf_launch_global(plan.lane, QUADS, TRIS, CSG, ALIAS, TALLY, cam_rays, sc, cam, a, plan.dyn, n, stream, tb, t_ev_start, t_ev_stop);
 }
 static hipError_t launch_fused(const DevScene& sc, const DevCamera& cam, const WfArgs& a, bool primary, unsigned n,
                                hipStream_t stream, bool tally, const WfTuning& tn, WfImagePlan* ran) {
   // QUADS: solids outside the hierarchies, or the hierarchy over the other records
   const bool quads = sc.n_fx_quads > 0 || sc.n_obvh > 0 || sc.n_lbvh > 0;
+  if (sc.n_alias_rec > 0)  // (the Csg kernels with the alias classes)
+    return tally ? launch_fused_q<true, true, true, true, true>(sc, cam, a, primary, n, stream, tn, ran)
+                 : launch_fused_q<true, false, true, true, true>(sc, cam, a, primary, n, stream, tn, ran);
   if (sc.n_csg_units > 0)  // (the triangle kernels with the Csg units)
     return tally ? launch_fused_q<true, true, true, true>(sc, cam, a, primary, n, stream, tn, ran)
                  : launch_fused_q<true, false, true, true>(sc, cam, a, primary, n, stream, tn, ran);
@@ -459,10 +463,12 @@ hipError_t Wavefront::render(const DevScene& sc, const WfJob& job, hipStream_t s
   if (timed) WF_CHECK(hipEventRecord(ev1_, stream));
   lr_.L = (unsigned)sc.n_lights; lr_.n0 = n0; lr_.max_depth = max_depth;
   lr_.counted = count; lr_.exact_disc = !bvh && !skip_shadow; lr_.bvh = bvh;
-  // (the leaves under Csg units count with their kinds: the reference tests them too)
-  lr_.n_diag = (unsigned long long)sc.n_diag; lr_.n_gen = (unsigned long long)sc.n_gen + (unsigned long long)sc.n_csg_sph;
-  lr_.n_planes = (unsigned long long)sc.n_planes + (unsigned long long)sc.n_csg_planes;
-  lr_.n_quads = (unsigned long long)sc.n_quads + (unsigned long long)sc.n_tris + (unsigned long long)sc.n_csg_other;
+  // (the leaves under Csg units and the alias classes' members count with their kinds: the reference tests them too)
+  lr_.n_diag = (unsigned long long)sc.n_diag;
+  lr_.n_gen = (unsigned long long)sc.n_gen + (unsigned long long)sc.n_csg_sph + (unsigned long long)sc.n_alias_sph;
+  lr_.n_planes = (unsigned long long)sc.n_planes + (unsigned long long)sc.n_csg_planes + (unsigned long long)sc.n_alias_planes;
+  lr_.n_quads = (unsigned long long)sc.n_quads + (unsigned long long)sc.n_tris + (unsigned long long)sc.n_csg_other +
+                (unsigned long long)sc.n_alias_other;
   return hipSuccess;
 }
 
@@ -682,7 +688,8 @@ hipError_t Wavefront::render_exhaustive(const DevScene& sc, const WfJob& job, hi
     a.disc_slot = (unsigned)ccls;
     prof_rays_[ccls] += n;
     WF_CHECK(pmark(stream, ccls, true));
-    if (sc.n_csg_units > 0) WF_CHECK((launch_closest_exh<true, true>(sc, cam, a, prim_launch, gen_lds, n, stream, tn)));
+    if (sc.n_alias_rec > 0) WF_CHECK((launch_closest_exh<true, true, true>(sc, cam, a, prim_launch, gen_lds, n, stream, tn)));
+    else if (sc.n_csg_units > 0) WF_CHECK((launch_closest_exh<true, true>(sc, cam, a, prim_launch, gen_lds, n, stream, tn)));
     else if (sc.n_quads > 0 || sc.n_tris > 0) WF_CHECK(launch_closest_exh<true>(sc, cam, a, prim_launch, gen_lds, n, stream, tn));
     else WF_CHECK(launch_closest_exh<false>(sc, cam, a, prim_launch, gen_lds, n, stream, tn));
     WF_CHECK(pmark(stream, ccls, false));
@@ -716,7 +723,8 @@ hipError_t Wavefront::render_exhaustive(const DevScene& sc, const WfJob& job, hi
         forked = true;
       }
       WF_CHECK(pmark(sh_stream, WF_SHADOW, true));
-      if (sc.n_csg_units > 0) WF_CHECK((launch_shadow_exh<true, true>(sc, a, gen_lds, sh_stream, tn)));
+      if (sc.n_alias_rec > 0) WF_CHECK((launch_shadow_exh<true, true, true>(sc, a, gen_lds, sh_stream, tn)));
+      else if (sc.n_csg_units > 0) WF_CHECK((launch_shadow_exh<true, true>(sc, a, gen_lds, sh_stream, tn)));
       else if (sc.n_quads > 0 || sc.n_tris > 0) WF_CHECK(launch_shadow_exh<true>(sc, a, gen_lds, sh_stream, tn));
       else WF_CHECK(launch_shadow_exh<false>(sc, a, gen_lds, sh_stream, tn));
       WF_CHECK(pmark(sh_stream, WF_SHADOW, false));

@@ -135,7 +135,7 @@ struct WfImagePlan {
 // built without the scheduler's trackers). e0/e1: launch-carried profiling
 // events, or null.
 struct WfArgs;
-hipError_t wf_launch_global(int lane, bool quads, bool tris, bool csg, bool tally, bool cam_rays, const DevScene& sc, const DevCamera& cam,
+hipError_t wf_launch_global(int lane, bool quads, bool tris, bool csg, bool alias, bool tally, bool cam_rays, const DevScene& sc, const DevCamera& cam,
                             const WfArgs& a, size_t dyn, unsigned n, hipStream_t stream, int block, hipEvent_t e0,
                             hipEvent_t e1);
 

@@ -310,7 +310,7 @@ __device__ WfLds wf_lds_stage(const DevScene& sc, const PrimRec* prim, unsigned 
 // or the shadow-caster variant). Sphere records are read as wave-uniform
 // ds_read_b128 broadcasts with a one-record look-ahead; the image holds zero
 // padding records, so record j+1 always exists.
-template <bool PRIMARY, bool SHADOW, bool QUADS, bool CSG = false>
+template <bool PRIMARY, bool SHADOW, bool QUADS, bool CSG = false, bool ALIAS = false>
 __device__ __forceinline__ void wf_trace_lds(const DevScene& sc, const WfLds& lv, V3 o, V3 d, Hit& h,
                                              unsigned& n_disc, GateSkips& sk) {
   hit_init(h);
@@ -384,7 +384,9 @@ __device__ __forceinline__ void wf_trace_lds(const DevScene& sc, const WfLds& lv
     }
   }
   if constexpr (CSG) csg_units<SHADOW, false>(sc, sc.csg_units, sc.n_csg_units, o, d, h, n_disc, &sk);
+  if constexpr (ALIAS) alias_classes<SHADOW>(sc, o, d, h, n_disc, &sk);
   hit_finish(h);
+  if constexpr (ALIAS && !SHADOW) alias_finish(sc, h);
 }
 
 // The counted launches' group skips (GateSkips), summed per wave into the
@@ -400,7 +402,7 @@ __device__ __forceinline__ void add_gate_skips(WfCounters* cnt, const GateSkips&
 }
 
 // ---------------------------------------------------------- trace kernels
-template <bool USE_LDS, bool PRIMARY, bool QUADS, int TW, bool CSG = false>
+template <bool USE_LDS, bool PRIMARY, bool QUADS, int TW, bool CSG = false, bool ALIAS = false>
 __global__ __launch_bounds__(kTraceBlock, TW) void wf_trace_closest(DevScene sc, DevCamera cam, WfArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   unsigned n_disc = 0;
@@ -415,8 +417,8 @@ __global__ __launch_bounds__(kTraceBlock, TW) void wf_trace_closest(DevScene sc,
     V3 o, d;
     wf_ray(a, cam, slot, o, d);
     Hit h;
-    if constexpr (USE_LDS) wf_trace_lds<PRIMARY, false, QUADS, CSG>(sc, lv, o, d, h, n_disc, sk);
-    else trace<false, QUADS, CSG>(sc, o, d, h, n_disc, &sk);
+    if constexpr (USE_LDS) wf_trace_lds<PRIMARY, false, QUADS, CSG, ALIAS>(sc, lv, o, d, h, n_disc, sk);
+    else trace<false, QUADS, CSG, ALIAS>(sc, o, d, h, n_disc, &sk);
     WfHit w;
     w.t = h.t; w.key = h.key; w.c1k = h.c1k; w.c2k = h.c2k; w.hin = h.hin;
     a.hits[slot] = w;
@@ -430,7 +432,7 @@ __global__ __launch_bounds__(kTraceBlock, TW) void wf_trace_closest(DevScene sc,
 // object has a root t with 0 <= t < distance (the first t >= 0 among shadow
 // casters in the sorted list is the minimum one). Full traversal: the exact
 // counters (sphere_disc_ge0) need every test.
-template <bool USE_LDS, bool QUADS, int TW, bool CSG = false>
+template <bool USE_LDS, bool QUADS, int TW, bool CSG = false, bool ALIAS = false>
 __global__ __launch_bounds__(kTraceBlock, TW) void wf_trace_shadow(DevScene sc, WfArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   unsigned n_disc = 0;
@@ -446,8 +448,8 @@ __global__ __launch_bounds__(kTraceBlock, TW) void wf_trace_shadow(DevScene sc, 
     unsigned slot;
     shadow_ray(sc, a, shard_slot<false>(pre, a.sh_cap, i), o, d, dist, slot);
     Hit h;
-    if constexpr (USE_LDS) wf_trace_lds<false, true, QUADS, CSG>(sc, lv, o, d, h, n_disc, sk);
-    else trace<true, QUADS, CSG>(sc, o, d, h, n_disc, &sk);
+    if constexpr (USE_LDS) wf_trace_lds<false, true, QUADS, CSG, ALIAS>(sc, lv, o, d, h, n_disc, sk);
+    else trace<true, QUADS, CSG, ALIAS>(sc, o, d, h, n_disc, &sk);
     shadow_result(sc, a, slot, h.key >= 0 && h.t < dist, o, d);
   }
   const unsigned long long s = wave_sum(n_disc);
@@ -666,8 +668,8 @@ struct FusedTally {
 // either the final colour (no children) or a ParentRec. Every lane of the wave
 // calls it (shard_append), `valid` false for the padding lanes. TALLY: the
 // kernel's (a counted launch; shadow_trace then counts every group gate).
-// TRIS, CSG: the kernel's (a scene with triangles, with Csg units).
-template <bool QUADS, bool CAM, bool TALLY, bool TRIS, bool CSG, typename Image>
+// TRIS, CSG, ALIAS: the kernel's (a scene with triangles, with Csg units, with alias classes).
+template <bool QUADS, bool CAM, bool TALLY, bool TRIS, bool CSG, bool ALIAS, typename Image>
 __device__ __forceinline__ void shade_fused(const DevScene& sc, const DevCamera& cam, const WfArgs& a,
                                             const Image& img, unsigned q, unsigned slot, bool valid, V3 o, V3 d,
                                             const Hit& h, FusedTally& t) {
@@ -736,7 +738,7 @@ __device__ __forceinline__ void shade_fused(const DevScene& sc, const DevCamera&
     if (a.skip_shadow && shadow_irrelevant(*m, Lr, sdir, c.normal, term)) {
       // the light is behind the surface: lighting() is the ambient term either way
     } else {
-      const bool shadowed = shadow_trace<QUADS, TALLY, TRIS, CSG>(
+      const bool shadowed = shadow_trace<QUADS, TALLY, TRIS, CSG, ALIAS>(
           sc, a.use_lb, img, l, c.over, sdir, dist, t.sh_disc, t.sh_tests, t.sh_boxes, &t.gsk, own_first,
           own_out >= 0 && vdot(sdir, c.normal) >= 0.0 ? own_out : -1);
       if (QUADS && a.count) count_hier_gates<TRIS, CSG>(sc, c.over, sdir, t.gsk);
@@ -772,7 +774,11 @@ __device__ __forceinline__ void shade_fused(const DevScene& sc, const DevCamera&
 // triangle walk (profiles/mesh_resources.txt).
 // CSG (with QUADS and TRIS): the scene has Csg units; the one combination, again a flag of
 // its own (profiles/csg_resources.txt).
-template <bool PRIMARY, bool QUADS, int LANE, bool TALLY, bool CAM = PRIMARY, bool TRIS = false, bool CSG = false>
+// ALIAS (with QUADS, TRIS and CSG): the scene has alias classes (rt_scene_create_aliased); one
+// more class of kernels on top, so that every other world keeps the kernels it had
+// (profiles/alias_resources.txt).
+template <bool PRIMARY, bool QUADS, int LANE, bool TALLY, bool CAM = PRIMARY, bool TRIS = false, bool CSG = false,
+          bool ALIAS = false>
 __global__ __launch_bounds__(kTraceBlock, 4) void wf_trace_fused(DevScene sc, DevCamera cam, WfArgs a) {
   __shared__ int stack_lds[lane_static_lds_bytes(LANE) ? lane_static_lds_bytes(LANE) / 4 : 1];  // (1: never read)
   extern __shared__ __attribute__((aligned(16))) unsigned char lane_dyn[];
@@ -839,7 +845,7 @@ __global__ __launch_bounds__(kTraceBlock, 4) void wf_trace_fused(DevScene sc, De
                                       t.tests, t.boxes);
       }
       // (a per-lane walk: planes and the other records first, an early nearest hit tightens the culling)
-      trace_rest<false, QUADS, true, TRIS, CSG>(sc, o, d, h, t.disc, &t.gsk);
+      trace_rest<false, QUADS, true, TRIS, CSG, ALIAS>(sc, o, d, h, t.disc, &t.gsk);
       if constexpr (QUADS) {
         other_trace<false>(sc, o, d, 0.0, h, t.disc, t.tests, t.boxes);
         line_trace<false>(sc, o, d, 0.0, h, t.tests, t.boxes);
@@ -849,6 +855,7 @@ __global__ __launch_bounds__(kTraceBlock, 4) void wf_trace_fused(DevScene sc, De
       if constexpr (Image::kPerLane) img.template walk<false>(sc, o, d, 0.0, h, t.disc, t.tests, t.boxes);
     }
     hit_finish(h);
+    if constexpr (ALIAS) alias_finish(sc, h);
   };
   while (c < n_chunks) {
     unsigned k_next = 0;
@@ -860,7 +867,7 @@ __global__ __launch_bounds__(kTraceBlock, 4) void wf_trace_fused(DevScene sc, De
     V3 o = v3(0, 0, 0), d = v3(0, 0, 0);
     Hit h;
     traverse(i, valid, slot, o, d, h);
-    shade_fused<QUADS, CAM, TALLY, TRIS, CSG>(sc, cam, a, img, c, slot, valid, o, d, h, t);
+    shade_fused<QUADS, CAM, TALLY, TRIS, CSG, ALIAS>(sc, cam, a, img, c, slot, valid, o, d, h, t);
     c = dyn ? c_base + X * (unsigned)__shfl((int)k_next, 0, 64) : c + W;
   }
   if constexpr (!TALLY) return;
