@@ -152,12 +152,17 @@ typedef struct rt_node_desc {
   double inverse[16];
 } rt_node_desc;
 
-/* Compile-time caps of the Csg evaluation (one per-ray survivor list of
- * RT_CSG_MAX_LEAVES * 4 entries): the primitives under one Csg that has no Csg
- * above it, and the Csg nodes on any path down from it (Groups between them
- * are free). rt_scene_create_tree refuses a world beyond either. */
+/* Compile-time caps of the Csg evaluation, per Csg that has no Csg above it:
+ * RT_CSG_MAX_LEAVES counts the primitives of kinds Sphere .. Cone under it (one
+ * per-ray survivor list of RT_CSG_MAX_LEAVES * 4 entries; Triangles and
+ * SmoothTriangles under it are not counted and have no cap), RT_CSG_MAX_DEPTH
+ * the Csg nodes on any path down from it (Groups between them are free), and,
+ * when a Triangle or SmoothTriangle lies under it, RT_CSG_MAX_NODES the Csg
+ * nodes below and including it (one "inside left" and one "inside right" bit
+ * per node). rt_scene_create_tree refuses a world beyond any of them. */
 #define RT_CSG_MAX_LEAVES 16
 #define RT_CSG_MAX_DEPTH 4
+#define RT_CSG_MAX_NODES 32
 
 /* The vertices of a `Triangle` (triangle.rs:24-44) or `SmoothTriangle`
  * (smooth_triangle.rs:27-55) in object space; its rt_shape_desc carries the
@@ -281,10 +286,20 @@ int rt_scene_create_mesh(const rt_shape_desc* shapes, size_t n_shapes,
  * left's before right's, each list in its own order) and filtered by
  * Csg::filter_intersections (csg.rs:71-91), nested Csgs bottom-up; normals,
  * patterns, materials and has_shadow are the leaf's own (geometry/mod.rs:51-56;
- * the enclosing Csgs' transforms take no part, as there).
- * RT_ERR_UNSUPPORTED_SHAPE: a Triangle / SmoothTriangle under a Csg; more than
- * RT_CSG_MAX_LEAVES primitives under one outermost Csg; more than
- * RT_CSG_MAX_DEPTH nested Csgs. The message names the cap. */
+ * the enclosing Csgs' transforms take no part, as there; a SmoothTriangle's u
+ * and v are those of the ray it was handed, chained down the Csgs above it).
+ * Triangles and SmoothTriangles (OBJ meshes) may lie under a Csg inside Groups
+ * at any depth, in any number; such a Csg is evaluated per ray in batches and
+ * is kept out of the Csgs' culling hierarchy (every ray that meets the
+ * reference's own Csg box tests its triangles).
+ * RT_ERR_UNSUPPORTED_SHAPE: a Triangle / SmoothTriangle whose innermost node is
+ * a Csg (a lone triangle as a Csg's own left or right child: put it in a
+ * Group, as a mesh is); more than RT_CSG_MAX_LEAVES primitives of kinds
+ * Sphere .. Cone under one outermost Csg; more than RT_CSG_MAX_DEPTH nested
+ * Csgs; more than RT_CSG_MAX_NODES Csg nodes in an outermost Csg with a
+ * triangle below it. The message names the cap.
+ * RT_ERR_DUPLICATE_SHAPES: as the other entry points, two shapes that may be
+ * structurally equal, two triangles under a Csg included. */
 int rt_scene_create_tree(const rt_shape_desc* shapes, size_t n_shapes,
                          const int32_t* shape_node, const int32_t* shape_side,
                          const rt_node_desc* nodes, size_t n_nodes,

@@ -19,6 +19,9 @@ int g_lb_res = -1;
 // the other hierarchies' kMinHierRecords; profiles/csg_hier_ab.txt)
 constexpr int kCsgHierMinDefault = 16;
 int g_csg_hier_min = kCsgHierMinDefault;
+// every Csg unit through the wide units' streamed evaluator, out of the units' hierarchy
+// ("csg_wide_all": the cross-check of csg_wide_eval against csg_unit_eval; off by default)
+int g_csg_wide_all = 0;
 std::mutex g_tune_mu;
 WfTuning g_tune_defaults;
 
@@ -210,6 +213,11 @@ int rtamd_tuning_set(const char* key, int value) {
     if (value < 0 || value > 65536)
       return fail(RT_ERR_INVALID_ARGUMENT, "csg_hier_min must be in [1, 65536], or 0 for the default");
     g_csg_hier_min = value ? value : kCsgHierMinDefault;
+    return RT_OK;
+  }
+  if (key && std::strcmp(key, "csg_wide_all") == 0) {
+    if (value < 0 || value > 1) return fail(RT_ERR_INVALID_ARGUMENT, "csg_wide_all must be 0 or 1");
+    g_csg_wide_all = value;
     return RT_OK;
   }
   std::lock_guard<std::mutex> lk(g_tune_mu);

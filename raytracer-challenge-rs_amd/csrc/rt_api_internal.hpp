@@ -51,6 +51,7 @@ extern int g_bvh_leaf;  // BVH leaf size; 0 = automatic: 2, or 1 when the LDS im
 extern int g_bvh_ct;    // SAH node-visit cost in percent of a sphere test
 extern int g_lb_res;    // light-buffer cells per cube-map face edge: 0 = none, -1 = by scene size
 extern int g_csg_hier_min;  // boxed Csg units from which their hierarchy is built
+extern int g_csg_wide_all;  // every Csg unit through the wide units' evaluator (development cross-check)
 // render-time tuning copied into every scene at its creation (rt_scene::tune)
 extern std::mutex g_tune_mu;
 extern WfTuning g_tune_defaults;

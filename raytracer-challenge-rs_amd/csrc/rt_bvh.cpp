@@ -801,6 +801,7 @@ bool csg_unit_box(const CsgOp* ops, int first, int n, const CsgRec* nodes, const
       if (--lvl < 0) return false;
       continue;
     }
+    if (op.code == kCsgTri) return false;  // a wide unit: behind its own Csg gate in the loop
     if (op.code != kCsgLeaf) continue;  // a group's gate moves no ray
     const OtherRec& r = leaves[op.arg];
     // planes are unbounded; a cone's a ~ 0 branch pushes a root off the cone (other_box)

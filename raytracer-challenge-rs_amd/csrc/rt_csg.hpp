@@ -28,7 +28,7 @@ enum { kCsgUnion = 0, kCsgIntersection = 1, kCsgDifference = 2 };  // Operation 
 
 // Compile-time caps of one unit (a Csg with no Csg above it); a world beyond one
 // is refused when the scene is created (rt_scene_create_tree).
-constexpr int kCsgMaxLeaves = 16;  // primitives under one unit
+constexpr int kCsgMaxLeaves = 16;  // primitives of kinds 0-4 under one unit (its triangles are not counted)
 constexpr int kCsgMaxDepth = 4;    // Csg nodes on a path from the unit down (groups between them are free)
 // A leaf yields at most 4 intersections (list position 0..3, kKeyShift)
 constexpr int kCsgListCap = kCsgMaxLeaves * (1 << kKeyShift);
@@ -95,6 +95,87 @@ RT_CSG_FN void csg_filter(CsgList& xs, int start, int op, int32_t split) {
 RT_CSG_FN void csg_close(CsgList& xs, int start, int op, int32_t split) {
   csg_sort(xs, start);
   csg_filter(xs, start, op, split);
+}
+
+// ---- The stream form, for a WIDE unit (one with triangle leaves: its list has no
+// small bound). The nested "sort left ++ right, filter, hand up" is one global order,
+// ascending (t, key): a unit's leaves have consecutive object indices depth first, so
+// every node's stable sort orders equal t by key, each node's list is a subsequence of
+// that order, and a node sees exactly what every node below it let through. So the
+// roots can be taken in ascending (t, key), a batch at a time, and each one sent up its
+// chain of enclosing Csg nodes, innermost first, until a node drops it: the nodes above
+// a drop never see it, and their state does not move. Per node the state is the two
+// bits of filter_intersections, `inl` and `inr`: one bit per node of the unit in two
+// words, hence the cap.
+constexpr int kCsgMaxNodes = 32;  // Csg nodes in one wide unit
+
+// A batch entry's tag: the innermost Csg node above its leaf (the unit's node number,
+// < kCsgMaxNodes), and the leaf's place in the fold's table: its number among the unit's
+// leaves of kinds 0-4 (< kCsgMaxLeaves), or kCsgTagTri for a triangle (one root, no place).
+constexpr int kCsgTagNode = 31, kCsgTagSlotShift = 5, kCsgTagSlot = 15, kCsgTagTri = 1 << 9;
+struct CsgBatch {
+  CsgList xs;
+  uint16_t tag[kCsgListCap];
+};
+
+RT_CSG_FN bool csg_above(double t, int32_t key, double wt, int32_t wk) { return t > wt || (t == wt && key > wk); }
+
+// One root into the batch of the `cap` smallest (t, key) above the watermark (wt, wk),
+// kept ascending by insertion; `more`: a root above the watermark was left out (walk
+// again from the batch's last entry). A NaN t is above no watermark (the reference's
+// sort panics on one).
+RT_CSG_FN void csg_batch_insert(CsgBatch& b, int cap, double t, int32_t key, uint16_t tag, double wt, int32_t wk,
+                                bool& more) {
+  if (!csg_above(t, key, wt, wk)) return;
+  CsgList& xs = b.xs;
+  int j = xs.n;
+  if (xs.n >= cap) {
+    more = true;
+    if (csg_above(t, key, xs.t[cap - 1], xs.key[cap - 1])) return;
+    j = cap - 1;  // the last entry falls out
+  } else {
+    ++xs.n;
+  }
+  while (j > 0 && csg_above(xs.t[j - 1], xs.key[j - 1], t, key)) {
+    xs.t[j] = xs.t[j - 1];
+    xs.key[j] = xs.key[j - 1];
+    b.tag[j] = b.tag[j - 1];
+    --j;
+  }
+  xs.t[j] = t;
+  xs.key[j] = key;
+  b.tag[j] = tag;
+}
+
+// One root of the stream up its chain: `nodes` the unit's CsgRecs (the unit's own
+// first), `node` the innermost one above the root's leaf. At each node lhit from its
+// split, the truth table, then the toggle (csg.rs:71-91); false at the first drop.
+RT_CSG_FN bool csg_stream_pass(const CsgRec* nodes, int node, int32_t key, uint32_t& inl, uint32_t& inr) {
+  const int32_t obj = key >> kKeyShift;
+  for (int g = node; g >= 0; g = nodes[g].parent) {
+    const uint32_t bit = 1u << g;
+    const bool lhit = obj < nodes[g].split;
+    const bool ok = csg_allowed(nodes[g].op, lhit, (inl & bit) != 0, (inr & bit) != 0);
+    if (lhit) inl ^= bit;
+    else inr ^= bit;
+    if (!ok) return false;
+  }
+  return true;
+}
+
+// The streamed fold's table: per leaf of kinds 0-4 (by its place) the count of its
+// survivors t < 0 so far and the last of them. The stream is ascending, so when a
+// survivor t >= 0 arrives every survivor t < 0 of its leaf has been counted (`hin`), and
+// at the end a leaf with an odd count is a container candidate at its last one.
+struct CsgNegTable {
+  double t[kCsgMaxLeaves];
+  int32_t key[kCsgMaxLeaves];
+  uint32_t odd;  // bit s: leaf s has an odd number of survivors t < 0
+};
+RT_CSG_FN void csg_neg_note(CsgNegTable& nt, int slot, double t, int32_t key) {
+  nt.t[slot] = t;
+  nt.key[slot] = key;
+  nt.odd ^= 1u << slot;
 }
 
 }  // namespace rtamd

@@ -357,11 +357,37 @@ struct GateSkips {
 
 // ------------------------------------------------------------------- Csg
 __device__ __forceinline__ void csg_skip(GateSkips& sk, int counts) {
-  sk.sph += counts & 255; sk.plane += (counts >> 8) & 255; sk.other += (counts >> 16) & 255;
+  sk.sph += counts & 31; sk.plane += (counts >> 5) & 31; sk.other += (unsigned)counts >> 10;
 }
-// Shape::intersect (geometry/mod.rs:46-49) of one leaf under a Csg, appended to
-// the list in push order: the sphere's roots as sphere_adc forms them, the
+// Shape::intersect (geometry/mod.rs:46-49) of one leaf of kinds 0-4 under a Csg: its
+// list in push order into t[0..n): the sphere's roots as sphere_adc forms them, the
 // plane's as plane_test, the solids' as quad_test (quad_local_intersect).
+__device__ __forceinline__ int csg_leaf_roots(const OtherRec* q, V3 o, V3 d, double t[4], unsigned& n_disc) {
+  const double* m = q->m;
+  const V3 lo = m34_point(m, o);
+  const V3 ld = v3(m[0] * d.x + m[1] * d.y + m[2] * d.z, m[4] * d.x + m[5] * d.y + m[6] * d.z,
+                   m[8] * d.x + m[9] * d.y + m[10] * d.z);
+  if (q->kind == 0) {  // sphere.rs:47-62
+    const double a = ld.x * ld.x + ld.y * ld.y + ld.z * ld.z;
+    const double dt = ld.x * lo.x + ld.y * lo.y + ld.z * lo.z;
+    const double c = lo.x * lo.x + lo.y * lo.y + lo.z * lo.z - 1.0;
+    const double disc = dt * dt - a * c;
+    if (!(disc >= 0.0)) return 0;
+    ++n_disc;
+    const double s = sqrt(disc);
+    t[0] = (-dt - s) / a;
+    t[1] = (-dt + s) / a;
+    return 2;
+  }
+  if (q->kind == 1) {  // plane.rs:53-60
+    if (fabs(ld.y) < kEpsilon) return 0;
+    t[0] = -lo.y / ld.y;
+    return 1;
+  }
+  return quad_local_intersect(q->kind, q->minimum, q->maximum, q->closed != 0, lo, ld, t);
+}
+// The same roots appended to the narrow evaluator's list in push order (a sphere's and a
+// plane's straight from their registers).
 __device__ __forceinline__ void csg_leaf(const OtherRec* q, V3 o, V3 d, CsgList& xs, unsigned& n_disc) {
   const double* m = q->m;
   const V3 lo = m34_point(m, o);
@@ -474,12 +500,127 @@ __device__ __forceinline__ void csg_unit_eval(const DevScene& sc, const CsgUnit 
         pc = op.skip_to;
         continue;
       }
-    } else {
+    } else if (op.code == kCsgLeaf) {  // (kCsgTri: a wide unit's, here only for its gates, COUNT_ONLY)
       if (!COUNT_ONLY) csg_leaf(sc.csg_leaves + op.arg, co, cd, xs, disc);
     }
     ++pc;
   }
   if (!COUNT_ONLY) csg_fold<SHADOW>(sc, xs, h);
+}
+// The same for a WIDE unit (rt_layout.hpp kCsgWide: one with triangle leaves, whose list
+// has no small bound), in the stream form of rt_csg.hpp. Each walk of the program (the
+// same chain of rays and the same gates as above) collects the kCsgListCap smallest roots
+// above a watermark (t, key), ascending; the batch goes through the nodes' filter bits
+// (csg_stream_pass) and the survivors fold into `h` as csg_fold folds them: the first
+// survivor t >= 0 (a shadow ray's: of a leaf that casts one) competes by (t, key), `hin` is
+// the parity of its leaf's survivors t < 0, a leaf with an odd number of those is a
+// container candidate at its last one (a triangle has one root: pushed at once; the
+// others at the end, CsgNegTable). When the walk left roots out, the watermark moves to
+// the batch's last entry and the program is walked again. It ends at the unit's hit, or at
+// the first root beyond the current h.t: nothing later is a hit, a container or `hin`.
+// The gate skips and sphere_disc_ge0 are the first walk's.
+__device__ __forceinline__ bool csg_tri_roots(const TriRec* q, V3 o, V3 d, double& t) {
+  const V3 lo = m34_point(q->m, o);
+  const V3 ld = v3(q->m[0] * d.x + q->m[1] * d.y + q->m[2] * d.z, q->m[4] * d.x + q->m[5] * d.y + q->m[6] * d.z,
+                   q->m[8] * d.x + q->m[9] * d.y + q->m[10] * d.z);
+  double u, v;
+  return tri_local_intersect(v3(q->p1[0], q->p1[1], q->p1[2]), v3(q->e1[0], q->e1[1], q->e1[2]),
+                             v3(q->e2[0], q->e2[1], q->e2[2]), lo, ld, t, u, v);
+}
+template <bool SHADOW>
+__device__ __forceinline__ void csg_wide_eval(const DevScene& sc, const CsgUnit un, V3 o, V3 d, Hit& h, unsigned& disc,
+                                              GateSkips& sk) {
+  CsgBatch b;
+  CsgNegTable nt;
+  nt.odd = 0;
+  uint32_t inl = 0, inr = 0;
+  double wt = -INFINITY;  // below every root: (t, key) > (-inf, -1)
+  int32_t wk = -1;
+  const int end = un.first + un.n;
+  const CsgRec* nodes = sc.csg_nodes + sc.csg_ops[un.first].arg;  // the unit's own node first
+  bool first = true;
+  for (;;) {
+    b.xs.n = 0;
+    bool more = false;
+    double ray[kCsgMaxDepth + 1][6];
+    int lvl = 0, node = -1;
+    V3 co = o, cd = d;
+    for (int pc = un.first; pc < end;) {
+      const CsgOp op = sc.csg_ops[pc];
+      if (op.code == kCsgEnter) {
+        const CsgRec* c = sc.csg_nodes + op.arg;
+        const V3 lo = m34_point(c->m, co);
+        const V3 ld = v3(c->m[0] * cd.x + c->m[1] * cd.y + c->m[2] * cd.z, c->m[4] * cd.x + c->m[5] * cd.y + c->m[6] * cd.z,
+                         c->m[8] * cd.x + c->m[9] * cd.y + c->m[10] * cd.z);
+        if (lvl >= kCsgMaxDepth || !bbox_intersects(c->lo, c->hi, lo, ld)) {  // csg.rs:116-118
+          if (first) csg_skip(sk, op.counts);
+          pc = op.skip_to;
+          continue;
+        }
+        ray[lvl][0] = co.x; ray[lvl][1] = co.y; ray[lvl][2] = co.z;
+        ray[lvl][3] = cd.x; ray[lvl][4] = cd.y; ray[lvl][5] = cd.z;
+        ++lvl;
+        node = c->self;
+        co = lo; cd = ld;
+      } else if (op.code == kCsgExit) {
+        --lvl;
+        node = nodes[node].parent;
+        co = v3(ray[lvl][0], ray[lvl][1], ray[lvl][2]);
+        cd = v3(ray[lvl][3], ray[lvl][4], ray[lvl][5]);
+      } else if (op.code == kCsgGroup) {
+        if (!bbox_intersects((cGroupRec)sc.groups + op.arg, co, cd)) {  // group.rs:50-52, the ray it is handed
+          if (first) csg_skip(sk, op.counts);
+          pc = op.skip_to;
+          continue;
+        }
+      } else if (op.code == kCsgTri) {
+        const TriRec* q = sc.csg_tris + op.arg;
+        double t;
+        if (csg_tri_roots(q, co, cd, t))
+          csg_batch_insert(b, kCsgListCap, t, (q->meta >> 1) << kKeyShift, (uint16_t)(node | kCsgTagTri), wt, wk, more);
+      } else {
+        const OtherRec* q = sc.csg_leaves + op.arg;
+        double t[4];
+        unsigned nd = 0;
+        const int n = csg_leaf_roots(q, co, cd, t, nd);
+        if (first) disc += nd;
+        const int k0 = (q->meta >> 1) << kKeyShift;
+        const uint16_t tag = (uint16_t)(node | q->gate << kCsgTagSlotShift);
+        for (int i = 0; i < n; ++i) csg_batch_insert(b, kCsgListCap, t[i], k0 + i, tag, wt, wk, more);
+      }
+      ++pc;
+    }
+    bool done = false;
+    for (int i = 0; i < b.xs.n && !done; ++i) {
+      const double t = b.xs.t[i];
+      const int key = b.xs.key[i];
+      const int tag = b.tag[i];
+      if (t > h.t) {
+        done = true;
+      } else if (csg_stream_pass(nodes, tag & kCsgTagNode, key, inl, inr)) {
+        const int slot = (tag >> kCsgTagSlotShift) & kCsgTagSlot;
+        if (t < 0.0) {
+          if (tag & kCsgTagTri) {
+            if (!SHADOW) push_container(h, t, key);
+          } else {
+            csg_neg_note(nt, slot, t, key);
+          }
+        } else if (!SHADOW || sc.shade[key >> kKeyShift].shadow) {
+          if (better(t, key, h.t, h.key)) {
+            h.t = t; h.key = key; h.hin = (tag & kCsgTagTri) ? 0 : (int)((nt.odd >> slot) & 1u);
+          }
+          done = true;
+        }
+      }
+    }
+    if (done || !more) break;
+    wt = b.xs.t[b.xs.n - 1];
+    wk = b.xs.key[b.xs.n - 1];
+    first = false;
+  }
+  if (!SHADOW)
+    for (int s = 0; s < kCsgMaxLeaves; ++s)
+      if ((nt.odd >> s) & 1u) push_container(h, nt.t[s], nt.key[s]);
 }
 // The units `units[0 .. n)`, each behind the gate of the groups around it (Group::intersect,
 // group.rs:49-58): the exhaustive paths pass the scene's full list in the reference's order,
@@ -490,12 +631,15 @@ __device__ __forceinline__ void csg_units(const DevScene& sc, const CsgUnit* uni
   GateSkips sk;
   unsigned disc = 0;
   for (int u = 0; u < n; ++u) {
-    const CsgUnit un = units[u];
+    CsgUnit un = units[u];
     if (un.gate && !group_gate(sc, un.gate, o, d)) {
       csg_skip(sk, un.counts);
       continue;
     }
-    csg_unit_eval<SHADOW, COUNT_ONLY>(sc, un, o, d, h, disc, sk);
+    const bool wide = (un.n & kCsgWide) != 0;
+    un.n &= ~kCsgWide;
+    if (!COUNT_ONLY && wide) csg_wide_eval<SHADOW>(sc, un, o, d, h, disc, sk);
+    else csg_unit_eval<SHADOW, COUNT_ONLY>(sc, un, o, d, h, disc, sk);  // (a wide unit's gates alone: the same walk)
   }
   n_disc += disc;
   if (skips) { skips->sph += sk.sph; skips->plane += sk.plane; skips->other += sk.other; }
@@ -809,10 +953,31 @@ __device__ __attribute__((noinline)) V3 tri_local_normal(const TriShade* tsp, co
   return vadd(vadd(vscale(n2, u), vscale(n3, v)), vscale(n1, 1.0 - u - v));
 }
 
+// A SmoothTriangle under a Csg: the intersection's u and v are those of the ray the
+// triangle was handed, the world ray through the inverse of each Csg above it, outermost
+// first, each one rounded (csg_wide_eval's chain), then the triangle's own. `node`: the
+// innermost CsgRec above it (TriShade::csg - 1); at most kCsgMaxDepth levels.
+__device__ __attribute__((noinline)) V3 csg_tri_local_normal(const CsgRec* node, const TriShade* tsp, const double* m, V3 o,
+                                                             V3 d) {
+  const CsgRec* unit = node - node->self;
+  int depth = 0;
+  for (int g = node->self; g >= 0; g = unit[g].parent) ++depth;
+  for (int lvl = depth - 1; lvl >= 0; --lvl) {
+    int g = node->self;
+    for (int k = 0; k < lvl; ++k) g = unit[g].parent;
+    const double* c = unit[g].m;
+    const V3 lo = m34_point(c, o);
+    d = v3(c[0] * d.x + c[1] * d.y + c[2] * d.z, c[4] * d.x + c[5] * d.y + c[6] * d.z, c[8] * d.x + c[9] * d.y + c[10] * d.z);
+    o = lo;
+  }
+  return tri_local_normal(tsp, m, 6, o, d);
+}
+
 // Intersection::prepare_computations (intersection.rs:53-105) with the exact
 // top-2 replacement of the containers walk.
 // TRIS = false: the kernels of scenes without triangles leave their normals out.
-template <bool TRIS = true>
+// CSG: the kernels of scenes with Csg units (a smooth triangle may lie under one).
+template <bool TRIS = true, bool CSG = false>
 __device__ __forceinline__ Comps prepare(const DevScene& sc, V3 o, V3 d, const Hit& h) {
   Comps c;
   const int obj = h.key >> kKeyShift;
@@ -823,8 +988,13 @@ __device__ __forceinline__ Comps prepare(const DevScene& sc, V3 o, V3 d, const H
   // Shape::normal_at (geometry/mod.rs:51-56)
   const V3 lp = m34_point(s.inv, c.point);
   V3 ln;
-  if (TRIS && s.kind >= 5) ln = tri_local_normal(sc.tri_shade + (s.pad0 - 1), s.inv, s.kind, o, d);
-  else ln = local_normal_at(s, lp);
+  if (TRIS && s.kind >= 5) {
+    const TriShade* ts = sc.tri_shade + (s.pad0 - 1);
+    if (CSG && s.kind == 6 && ts->csg) ln = csg_tri_local_normal(sc.csg_nodes + (ts->csg - 1), ts, s.inv, o, d);
+    else ln = tri_local_normal(ts, s.inv, s.kind, o, d);
+  } else {
+    ln = local_normal_at(s, lp);
+  }
   V3 n = vnormalize(m33_vector(s.invT, ln));
   c.inside = false;
   if (vdot(n, c.eyev) < 0.0) { c.inside = true; n = vneg(n); }

@@ -33,7 +33,7 @@ __device__ __forceinline__ void hit_body(const DevScene& sc, const double* rays,
   for (int k = 0; k < 24; ++k) r[k] = 0.0;
   r[0] = -1.0;
   if (h.key < 0) return;
-  const Comps c = prepare(sc, o, d, h);
+  const Comps c = prepare<true, CSG>(sc, o, d, h);
   r[0] = c.obj; r[1] = h.t;
   r[2] = c.point.x; r[3] = c.point.y; r[4] = c.point.z;
   r[5] = c.over.x; r[6] = c.over.y; r[7] = c.over.z;

@@ -78,11 +78,14 @@ constexpr double kTriDirMax = 2.0, kTriOriginMax = 16384.0;
 // index here, 0 for every other kind): the flat normal, the vertex normals of
 // the smooth kind, and p1 / e1 / e2 again, from which prepare() recomputes the
 // hit's u and v (tri_local_intersect's operations on the same operands).
+// `csg`: 1 + the innermost CsgRec above a triangle under a Csg (0: none): there the
+// reference's u and v are those of the ray chained down the Csgs (csg_tri_local_normal).
 struct alignas(64) TriShade {
   double normal[3];
   double n1[3], n2[3], n3[3];
   double p1[3], e1[3], e2[3];
-  double pad[3];
+  int32_t csg, pad0;
+  double pad[2];
 };
 static_assert(sizeof(TriShade) == 192, "TriShade must stay 192 B");
 static_assert(sizeof(GroupRec) == 64, "GroupRec must stay 64 B");
@@ -98,10 +101,16 @@ static_assert(sizeof(GroupRec) == 64, "GroupRec must stay 64 B");
 //              back to the enclosing ray
 //   kCsgGroup  arg = the GroupRec: Group::intersect's gate (group.rs:49-58) with
 //              the ray it is handed; a miss jumps to `skip_to`
-//   kCsgLeaf   arg = the leaf (an OtherRec: kind 0 sphere, 1 plane, 2-4 solids)
-// `counts`: the leaves below the node by counter class, sphere | plane << 8 |
-// other << 16 (a failed gate owes the reference's count of them, GateSkips).
-enum { kCsgEnter = 0, kCsgExit = 1, kCsgGroup = 2, kCsgLeaf = 3 };
+//   kCsgLeaf   arg = the leaf (an OtherRec: kind 0 sphere, 1 plane, 2-4 solids;
+//              its `gate` holds the leaf's number among these leaves of its unit)
+//   kCsgTri    arg = the leaf (a TriRec of DevScene::csg_tris: a Triangle or
+//              SmoothTriangle under a Csg): one root at list position 0
+// `counts`: the leaves below the node by counter class, sphere | plane << 5 |
+// other << 10 (a failed gate owes the reference's count of them, GateSkips):
+// at most kCsgMaxLeaves spheres and planes, the triangles of a mesh among the others.
+enum { kCsgEnter = 0, kCsgExit = 1, kCsgGroup = 2, kCsgLeaf = 3, kCsgTri = 4 };
+constexpr int32_t kCsgCountOtherMax = (1 << 22) - 1;
+inline int32_t csg_pack_counts(const int32_t* c) { return (int32_t)((uint32_t)c[0] | (uint32_t)c[1] << 5 | (uint32_t)c[2] << 10); }
 struct alignas(16) CsgOp {
   int32_t code, arg, skip_to, counts;
 };
@@ -109,15 +118,22 @@ struct alignas(16) CsgOp {
 // tests it, the operation (csg.rs:14-19) and `split`, the first object index of
 // its right child: an intersection's object is in `left` (Shape::includes,
 // geometry/mod.rs:87-89, group.rs:104-106, csg.rs:132-134) iff its index is below.
+// A unit's nodes are consecutive, the unit's own first; `self` is the node's number
+// among them and `parent` the number of the Csg above it (-1: the unit's own node).
 struct alignas(64) CsgRec {
   double m[12];
   double lo[3], hi[3];
   int32_t op, split;
-  int64_t pad[5];
+  int32_t parent, self;
+  int64_t pad[4];
 };
 static_assert(sizeof(CsgRec) == 192, "CsgRec must stay 192 B");
 // One unit: its program ops[first .. first + n), the gate of the groups around it
 // (as a record's `gate`), and its leaves by counter class (as CsgOp::counts).
+// `n` | kCsgWide: a WIDE unit (one with a triangle leaf, or every unit under the
+// development knob csg_wide_all): the streamed evaluator (csg_wide_eval), never the
+// units' hierarchy.
+constexpr int32_t kCsgWide = 1 << 30;
 struct alignas(16) CsgUnit {
   int32_t first, n, gate, counts;
 };
@@ -391,6 +407,7 @@ struct DevScene {
   const CsgOp* csg_ops;
   const CsgRec* csg_nodes;
   const OtherRec* csg_leaves;
+  const TriRec* csg_tris;  // the triangle leaves of the wide units (they are in no other list)
   int32_t n_csg_units, n_csg_sph, n_csg_planes, n_csg_other;
   // on the fast path the hierarchy over the units' padded world boxes (unit_trace; `urec`: the
   // boxed units' records in its leaf order) and the units it does not hold (`fx_units`, every

@@ -11,6 +11,9 @@
 
 using namespace rtapi;
 
+static_assert(kCsgMaxLeaves == RT_CSG_MAX_LEAVES && kCsgMaxDepth == RT_CSG_MAX_DEPTH && kCsgMaxNodes == RT_CSG_MAX_NODES,
+              "the Csg caps of include/rt_render.h are rt_csg.hpp's");
+
 namespace {
 
 bool is_diag_inverse(const double* inv) {
@@ -81,10 +84,14 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
     if (shapes[i].pattern_kind < RT_PATTERN_NONE || shapes[i].pattern_kind > RT_PATTERN_CHECKERS)
       return fail(RT_ERR_INVALID_ARGUMENT, "shape " + std::to_string(i) + ": bad pattern kind");
   }
-  // a shape under a Csg: a leaf of that Csg's unit (kinds 0-4 only)
+  // a shape under a Csg: a leaf of that Csg's unit. A unit with a triangle leaf is WIDE
+  // (csg_wide_eval): no cap on its triangles, kCsgMaxLeaves primitives of kinds 0-4 (the
+  // fold's table), kCsgMaxNodes Csg nodes (the filter's bits), as many `other` leaves as the
+  // counter packing holds. Every other unit is narrow: kinds 0-4 only, kCsgMaxLeaves of them.
   std::vector<int32_t> unit_of(n_shapes, -1);
+  std::vector<char> wide_unit(n_nodes, 0);
   if (any_csg) {
-    std::vector<int32_t> n_leaves(n_nodes, 0);
+    std::vector<int32_t> n_leaves(n_nodes, 0), n_other(n_nodes, 0), n_csg_nodes(n_nodes, 0);
     for (size_t i = 0; i < n_shapes; ++i) {
       const int32_t nd = shape_node[i];
       if (nd < 0) continue;
@@ -93,11 +100,29 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
       const int32_t u = unit_of_node[(size_t)nd];
       if (u < 0) continue;
       unit_of[i] = u;
-      if (shapes[i].kind > RT_SHAPE_CONE)
-        return fail(RT_ERR_UNSUPPORTED_SHAPE, "shape " + std::to_string(i) + ": a Triangle under a Csg is not supported");
+      if (shapes[i].kind > RT_SHAPE_PLANE && ++n_other[(size_t)u] > kCsgCountOtherMax)
+        return fail(RT_ERR_UNSUPPORTED_SHAPE, "node " + std::to_string(u) + ": more than " + std::to_string(kCsgCountOtherMax) +
+                                                  " triangles and solids under one Csg (the gates' counter packing)");
+      if (shapes[i].kind > RT_SHAPE_CONE) {
+        // a mesh is a Group (ObjParser's, Group::divide's): the one refusal kept is a lone triangle as a
+        // Csg's own left or right child, which the callers of this entry point were promised
+        if (nodes[nd].kind == RT_NODE_CSG)
+          return fail(RT_ERR_UNSUPPORTED_SHAPE, "shape " + std::to_string(i) +
+                                                    ": a Triangle under a Csg as its own left or right child is not "
+                                                    "supported: put it in a Group (triangles inside Groups under a Csg are)");
+        wide_unit[(size_t)u] = 1;
+        continue;
+      }
       if (++n_leaves[(size_t)u] > kCsgMaxLeaves)
         return fail(RT_ERR_UNSUPPORTED_SHAPE, "node " + std::to_string(u) + ": more than RT_CSG_MAX_LEAVES = " +
-                                                  std::to_string(kCsgMaxLeaves) + " primitives under one Csg");
+                                                  std::to_string(kCsgMaxLeaves) +
+                                                  " primitives under one Csg (Sphere, Plane, Cube, Cylinder, Cone; triangles are not counted)");
+    }
+    for (size_t g = 0; g < n_nodes; ++g) {
+      const int32_t u = unit_of_node[g];
+      if (u >= 0 && nodes[g].kind == RT_NODE_CSG && ++n_csg_nodes[(size_t)u] > kCsgMaxNodes && wide_unit[(size_t)u])
+        return fail(RT_ERR_UNSUPPORTED_SHAPE, "node " + std::to_string(u) + ": more than RT_CSG_MAX_NODES = " +
+                                                  std::to_string(kCsgMaxNodes) + " Csg nodes in one Csg with triangles below it");
     }
   }
   // the j-th triangle shape takes tri_descs[j]
@@ -168,8 +193,31 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
   std::vector<TriRec> tris;
   std::vector<TriShade> tri_shade;
   std::vector<ShadeRec> shade(n_shapes);
-  std::vector<OtherRec> csg_leaves;  // the leaves under Csg units live only here
+  std::vector<OtherRec> csg_leaves;  // the leaves under Csg units live only here ...
+  std::vector<TriRec> csg_tris;      // ... the triangles among them here: no hierarchy, light buffer or image knows them
   std::vector<int32_t> leaf_of(n_shapes, -1);
+  // Triangle::new / SmoothTriangle::new (triangle.rs:24-44, smooth_triangle.rs:27-55)
+  auto make_tri = [&](size_t i, int32_t gate) {
+    const rt_shape_desc& d = shapes[i];
+    const rt_triangle_desc& t = *tri_of[i];
+    const rt::Point p1(t.p1[0], t.p1[1], t.p1[2]), p2(t.p2[0], t.p2[1], t.p2[2]), p3(t.p3[0], t.p3[1], t.p3[2]);
+    const rt::Vector e1 = p2 - p1, e2 = p3 - p1, normal = rt::cross(e2, e1).normalize();
+    TriRec r{};
+    TriShade ts{};
+    for (int e = 0; e < 12; ++e) r.m[e] = d.inverse[e];
+    const double p[3] = {p1.x, p1.y, p1.z}, a[3] = {e1.x, e1.y, e1.z}, b[3] = {e2.x, e2.y, e2.z};
+    const double nn[3] = {normal.x, normal.y, normal.z};
+    for (int c = 0; c < 3; ++c) {
+      r.p1[c] = ts.p1[c] = p[c]; r.e1[c] = ts.e1[c] = a[c]; r.e2[c] = ts.e2[c] = b[c];
+      ts.normal[c] = nn[c]; ts.n1[c] = t.n1[c]; ts.n2[c] = t.n2[c]; ts.n3[c] = t.n3[c];
+    }
+    r.meta = (int32_t)(((int64_t)i << 1) | (d.casts_shadow ? 1 : 0));
+    r.gate = gate;
+    r.kind = d.kind;
+    r.tri = (int32_t)tri_shade.size();
+    tri_shade.push_back(ts);
+    return r;
+  };
   int32_t n_csg_kind[3] = {0, 0, 0};  // by counter class: spheres, planes, others
   // the alias classes' members, class by class (a class's members in object order); they enter
   // no other record list, so no sphere image, LDS plan, light buffer, own-sphere shadow rule or
@@ -203,6 +251,10 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
     const int32_t gate = gate_of(i);  // shapes inside groups: general records with their group gate
     if (class_of[i] >= 0) {  // a member of an alias class: only in its class's records (below)
       ++n_alias_kind[d.kind == RT_SHAPE_SPHERE ? 0 : d.kind == RT_SHAPE_PLANE ? 1 : 2];
+    } else if (unit_of[i] >= 0 && d.kind >= RT_SHAPE_TRIANGLE) {  // a wide unit's leaf (kCsgTri)
+      leaf_of[i] = (int32_t)csg_tris.size();
+      csg_tris.push_back(make_tri(i, 0));
+      ++n_csg_kind[2];
     } else if (unit_of[i] >= 0) {  // its gates are the unit's program's (csg_units)
       OtherRec r{};
       for (int e = 0; e < 12; ++e) r.m[e] = d.inverse[e];
@@ -235,25 +287,7 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
       r.gate = gate;
       planes.push_back(r);
     } else if (d.kind >= RT_SHAPE_TRIANGLE) {
-      // Triangle::new / SmoothTriangle::new (triangle.rs:24-44, smooth_triangle.rs:27-55)
-      const rt_triangle_desc& t = *tri_of[i];
-      const rt::Point p1(t.p1[0], t.p1[1], t.p1[2]), p2(t.p2[0], t.p2[1], t.p2[2]), p3(t.p3[0], t.p3[1], t.p3[2]);
-      const rt::Vector e1 = p2 - p1, e2 = p3 - p1, normal = rt::cross(e2, e1).normalize();
-      TriRec r{};
-      TriShade ts{};
-      for (int e = 0; e < 12; ++e) r.m[e] = d.inverse[e];
-      const double p[3] = {p1.x, p1.y, p1.z}, a[3] = {e1.x, e1.y, e1.z}, b[3] = {e2.x, e2.y, e2.z};
-      const double nn[3] = {normal.x, normal.y, normal.z};
-      for (int c = 0; c < 3; ++c) {
-        r.p1[c] = ts.p1[c] = p[c]; r.e1[c] = ts.e1[c] = a[c]; r.e2[c] = ts.e2[c] = b[c];
-        ts.normal[c] = nn[c]; ts.n1[c] = t.n1[c]; ts.n2[c] = t.n2[c]; ts.n3[c] = t.n3[c];
-      }
-      r.meta = (int32_t)meta;
-      r.gate = gate;
-      r.kind = d.kind;
-      r.tri = (int32_t)tri_shade.size();
-      tris.push_back(r);
-      tri_shade.push_back(ts);
+      tris.push_back(make_tri(i, gate));
     } else {
       QuadRec r{};
       for (int e = 0; e < 12; ++e) r.m[e] = d.inverse[e];
@@ -337,11 +371,11 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
       if (unit_of_node[g] >= 0 && unit_of_node[g] != (int32_t)g)
         kids[(size_t)nodes[g].parent].push_back(Child{first_shape[g], nodes[g].side, (int32_t)g, -1});
     for (auto& k : kids) std::stable_sort(k.begin(), k.end(), [](const Child& a, const Child& b) { return a.first < b.first; });
-    auto pack = [](const int32_t* c) { return c[0] | c[1] << 8 | c[2] << 16; };
-    int32_t next_shape = 0;
+    int32_t next_shape = 0, unit_rec = 0, next_slot = 0;
     bool in_order = true, two_sided = true;
-    // emits the node's subtree; cnt: its leaves by counter class
-    std::function<void(int32_t, int32_t*)> emit = [&](int32_t g, int32_t* cnt) {
+    // emits the node's subtree; cnt: its leaves by counter class; above: the CsgRec of the
+    // innermost Csg above the node (-1: none, the node is the unit's own)
+    std::function<void(int32_t, int32_t*, int32_t)> emit = [&](int32_t g, int32_t* cnt, int32_t above) {
       const rt_node_desc& nd = nodes[g];
       const size_t at = csg_ops.size();
       const bool csg = nd.kind == RT_NODE_CSG;
@@ -351,8 +385,11 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
         for (int e = 0; e < 12; ++e) r.m[e] = nd.inverse[e];
         for (int c = 0; c < 3; ++c) { r.lo[c] = nd.min[c]; r.hi[c] = nd.max[c]; }
         r.op = nd.operation;
+        r.self = rec - unit_rec;
+        r.parent = above < 0 ? -1 : above - unit_rec;
         csg_nodes.push_back(r);
       }
+      const int32_t inner = csg ? rec : above;  // the innermost Csg above this node's children
       csg_ops.push_back(CsgOp{csg ? kCsgEnter : kCsgGroup, csg ? rec : g, 0, 0});
       int32_t mine[3] = {0, 0, 0};
       int n_side[2] = {0, 0};
@@ -362,13 +399,20 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
           if (csg && c.side != pass) continue;
           ++n_side[pass];
           if (c.node >= 0) {
-            emit(c.node, mine);
+            emit(c.node, mine, inner);
           } else {
             in_order = in_order && c.shape == next_shape;
             next_shape = c.shape + 1;
             const int k = shapes[c.shape].kind;
+            const int32_t leaf = leaf_of[(size_t)c.shape];
             ++mine[k == RT_SHAPE_SPHERE ? 0 : k == RT_SHAPE_PLANE ? 1 : 2];
-            csg_ops.push_back(CsgOp{kCsgLeaf, leaf_of[(size_t)c.shape], 0, 0});
+            if (k >= RT_SHAPE_TRIANGLE) {
+              tri_shade[(size_t)csg_tris[(size_t)leaf].tri].csg = 1 + inner;
+              csg_ops.push_back(CsgOp{kCsgTri, leaf, 0, 0});
+            } else {
+              csg_leaves[(size_t)leaf].gate = next_slot++;  // its place in the wide fold's table (CsgNegTable)
+              csg_ops.push_back(CsgOp{kCsgLeaf, leaf, 0, 0});
+            }
           }
         }
       }
@@ -377,7 +421,7 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
         csg_ops.push_back(CsgOp{kCsgExit, rec, 0, 0});
       }
       csg_ops[at].skip_to = (int32_t)csg_ops.size();
-      csg_ops[at].counts = pack(mine);
+      csg_ops[at].counts = csg_pack_counts(mine);
       for (int c = 0; c < 3; ++c) cnt[c] += mine[c];
     };
     for (size_t g = 0; g < n_nodes; ++g) {
@@ -387,9 +431,12 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
       u.gate = nodes[g].parent + 1;
       int32_t cnt[3] = {0, 0, 0};
       next_shape = first_shape[g] == INT32_MAX ? 0 : first_shape[g];
-      emit((int32_t)g, cnt);
+      unit_rec = (int32_t)csg_nodes.size();
+      next_slot = 0;
+      emit((int32_t)g, cnt, -1);
       u.n = (int32_t)csg_ops.size() - u.first;
-      u.counts = pack(cnt);
+      if (wide_unit[g] || g_csg_wide_all) u.n |= kCsgWide;
+      u.counts = csg_pack_counts(cnt);
       csg_units.push_back(u);
     }
     if (!two_sided) return fail(RT_ERR_INVALID_ARGUMENT, "a Csg node needs exactly one left and one right child");
@@ -446,7 +493,8 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
   std::vector<CsgUnit> urec, fx_units;
   std::vector<double> unit_boxes;
   for (const CsgUnit& u : csg_units) {
-    if (csg_unit_box(csg_ops.data(), u.first, u.n, csg_nodes.data(), csg_leaves.data(), blo, bhi)) {
+    // (a wide unit has no box: it stays in the loop, behind the reference's own Csg gate)
+    if (!(u.n & kCsgWide) && csg_unit_box(csg_ops.data(), u.first, u.n, csg_nodes.data(), csg_leaves.data(), blo, bhi)) {
       urec.push_back(u);
       unit_boxes.insert(unit_boxes.end(), blo, blo + 3);
       unit_boxes.insert(unit_boxes.end(), bhi, bhi + 3);
@@ -542,7 +590,8 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
   const size_t o_ar = align(o_ux + (fx_units.size() + 1) * sizeof(CsgUnit));
   const size_t o_ac = align(o_ar + (alias_rec.size() + 1) * sizeof(OtherRec));
   const size_t o_ao = align(o_ac + (alias_tab.size() + 1) * sizeof(AliasClass));
-  const size_t total = align(o_ao + (alias_of.size() + 1) * sizeof(int32_t)) + 256;
+  const size_t o_ct = align(o_ao + (alias_of.size() + 1) * sizeof(int32_t));
+  const size_t total = align(o_ct + (csg_tris.size() + 1) * sizeof(TriRec)) + 256;
   std::vector<unsigned char> host(total, 0);
   if (!diag.empty()) std::memcpy(&host[o_diag], diag.data(), diag.size() * sizeof(SphereDiag));
   if (!gen.empty()) std::memcpy(&host[o_gen], gen.data(), gen.size() * sizeof(SphereGen));
@@ -595,6 +644,7 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
   if (!csg_ops.empty()) std::memcpy(&host[o_co], csg_ops.data(), csg_ops.size() * sizeof(CsgOp));
   if (!csg_nodes.empty()) std::memcpy(&host[o_cn], csg_nodes.data(), csg_nodes.size() * sizeof(CsgRec));
   if (!csg_leaves.empty()) std::memcpy(&host[o_cl], csg_leaves.data(), csg_leaves.size() * sizeof(OtherRec));
+  if (!csg_tris.empty()) std::memcpy(&host[o_ct], csg_tris.data(), csg_tris.size() * sizeof(TriRec));
   if (!ubvh.empty()) std::memcpy(&host[o_ub], ubvh.data(), ubvh.size() * sizeof(BvhNode));
   if (!urec.empty()) std::memcpy(&host[o_ur], urec.data(), urec.size() * sizeof(CsgUnit));
   if (!fx_units.empty()) std::memcpy(&host[o_ux], fx_units.data(), fx_units.size() * sizeof(CsgUnit));
@@ -690,6 +740,7 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
   s->dev.csg_ops = (const CsgOp*)(b + o_co);
   s->dev.csg_nodes = (const CsgRec*)(b + o_cn);
   s->dev.csg_leaves = (const OtherRec*)(b + o_cl);
+  s->dev.csg_tris = (const TriRec*)(b + o_ct);
   s->dev.n_csg_units = (int32_t)csg_units.size();
   s->dev.n_csg_sph = n_csg_kind[0];
   s->dev.n_csg_planes = n_csg_kind[1];

@@ -695,7 +695,10 @@ hipError_t Wavefront::render_exhaustive(const DevScene& sc, const WfJob& job, hi
     WF_CHECK(pmark(stream, ccls, false));
     // 2. prepare_computations + spawn
     WF_CHECK(pmark(stream, WF_PREP, true));
-    WF_LAUNCH(wf_prep, dim3(occupancy_grid(wf_prep, kWfBlock, 0, n)), dim3(kWfBlock), 0, stream, sc, cam, a);
+    if (sc.n_csg_units > 0)
+      WF_LAUNCH(wf_prep_csg, dim3(occupancy_grid(wf_prep_csg, kWfBlock, 0, n)), dim3(kWfBlock), 0, stream, sc, cam, a);
+    else
+      WF_LAUNCH(wf_prep, dim3(occupancy_grid(wf_prep, kWfBlock, 0, n)), dim3(kWfBlock), 0, stream, sc, cam, a);
     WF_CHECK(hipGetLastError());
     WF_CHECK(pmark(stream, WF_PREP, false));
     {  // the next generation's size and this one's shadow list, read back

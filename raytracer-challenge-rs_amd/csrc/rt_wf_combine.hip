@@ -77,6 +77,29 @@ __global__ __launch_bounds__(kWfBlock) void wf_prep(DevScene sc, DevCamera cam, 
     prep_one(sc, a, i, slot, valid, o, d, h);
   }
 }
+// The same for a scene with Csg units (prepare's chained u and v for a SmoothTriangle under one):
+// a kernel of its own, so that wf_prep keeps its code and registers.
+__global__ __launch_bounds__(kWfBlock) void wf_prep_csg(DevScene sc, DevCamera cam, WfArgs a) {
+  __shared__ unsigned s_pre[kPreRays];
+  const unsigned* pre = shard_prefix<true>(a.in_cnt, s_pre);
+  const unsigned stride = gridDim.x * blockDim.x;
+  // every lane of a wave runs the same number of iterations (appends are wave-wide)
+  const unsigned n_iter = (a.n + stride - 1) / stride;
+  unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
+  for (unsigned it = 0; it < n_iter; ++it, i += stride) {
+    const bool valid = i < a.n;
+    const unsigned slot = valid ? shard_slot<true>(pre, a.in_cap, i) : 0u;
+    V3 o = v3(0, 0, 0), d = v3(0, 0, 0);
+    Hit h;
+    h.key = -1;
+    if (valid) {
+      wf_ray(a, cam, slot, o, d);
+      const WfHit w = a.hits[slot];
+      h.t = w.t; h.key = w.key; h.hin = w.hin; h.c1k = w.c1k; h.c2k = w.c2k; h.c1t = 0; h.c2t = 0;
+    }
+    prep_one<true>(sc, a, i, slot, valid, o, d, h);
+  }
+}
 
 // ---------------------------------------------------------- combine
 // World::shade_hit (world.rs:40-68) from the node, the shadow flags and the

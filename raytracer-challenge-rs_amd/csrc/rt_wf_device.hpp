@@ -473,6 +473,8 @@ __device__ __forceinline__ bool ray_class_f(bool hit, const Comps& c) { return h
 // generation's rays. Every lane of the wave calls it (shard_append), `valid`
 // false for the padding lanes. wf_prep runs it on the stored hits; the BVH
 // trace kernels run it right after their traversal (no hit queue).
+// CSG: the scene has Csg units (wf_prep_csg; prepare's chained u and v).
+template <bool CSG = false>
 __device__ __forceinline__ void prep_one(const DevScene& sc, const WfArgs& a, unsigned i, unsigned slot, bool valid,
                                          V3 o, V3 d, const Hit& h) {
   const unsigned L = (unsigned)sc.n_lights;
@@ -483,7 +485,7 @@ __device__ __forceinline__ void prep_one(const DevScene& sc, const WfArgs& a, un
   const ShadeRec* m = nullptr;
   if (valid) {
     if (h.key >= 0) {
-      c = prepare(sc, o, d, h);
+      c = prepare<true, CSG>(sc, o, d, h);
       hit = true;
       m = &sc.shade[c.obj];
       // reflected_color (world.rs:107-114)
@@ -680,7 +682,7 @@ __device__ __forceinline__ void shade_fused(const DevScene& sc, const DevCamera&
   V3 refr_dir = v3(0, 0, 0);
   const ShadeRec* m = nullptr;
   if (valid && h.key >= 0) {
-    c = prepare<TRIS>(sc, o, d, h);
+    c = prepare<TRIS, CSG>(sc, o, d, h);
     hit = true;
     m = &sc.shade[c.obj];
     // reflected_color (world.rs:107-114)
@@ -900,6 +902,7 @@ __global__ void wf_frame_init(DevScene sc, DevCamera cam, PrimRec* prim, unsigne
                               unsigned n_a, uint4* zero_b, unsigned n_b, FrameTable tab, FrameTable* tab_dev,
                               unsigned n_frames, WfGenTab* gtab);
 __global__ void wf_prep(DevScene sc, DevCamera cam, WfArgs a);
+__global__ void wf_prep_csg(DevScene sc, DevCamera cam, WfArgs a);  // a scene with Csg units
 __global__ void wf_combine(DevScene sc, DevCamera cam, WfArgs a);
 __global__ void wf_combine_parents(DevScene sc, DevCamera cam, WfArgs a);
 __global__ void wf_average(WfArgs a, unsigned hsize, const double* colors, unsigned n_pix, double* out);

@@ -866,3 +866,166 @@ def csg_random(seed, width=24, height=16):
     w.add_light(rt.PointLight(rt.Point(-5, 8, -7), rt.Color(0.9, 0.9, 0.9)))
     w.add_light(rt.PointLight(rt.Point(6, 5, -4), rt.Color(0.4, 0.4, 0.4)))
     return w, _camera(width, height, PI / 3.0, (0.0, 1.5, -6.0), (0, 0.0, 0.5)), 4
+
+
+# ---- Triangles under a Csg (wide units: the streamed evaluator)
+def _mesh_group(text, material, divide=0):
+    g = rt.parse_obj_string(text).as_group()
+    g.set_material(material)
+    if divide:
+        g.divide(divide)
+    return g
+
+
+def csg_mesh_scene(width=640, height=360, nu=48, nv=32, divide=8, seed=0x5EED0C59, depth=5):
+    """Meshes under Csgs on a reflective floor: a divided mesh_torus(nu, nv) minus a cube; a smooth torus
+    intersected with a sphere under a rotated, unevenly scaled Csg; a glass torus minus a sphere; two
+    lights. The placement goes into the meshes' groups (set_transform bakes it into the triangles)."""
+    w = rt.World()
+    floor = rt.Plane()
+    floor.material.color = rt.Color(0.8, 0.8, 0.85)
+    floor.material.reflective = 0.25
+    floor.material.specular = 0.0
+    w.add_object(floor)
+    # a divided torus minus a cube
+    m = rt.Material()
+    m.color = rt.Color(0.9, 0.45, 0.2)
+    m.reflective = 0.15
+    a = _mesh_group(mesh_torus(nu, nv, False, seed), m)
+    a.set_transform(rt.translation(-2.4, 0.9, 0.6) * rt.rotation_x(0.5) * rt.scaling(0.9, 0.9, 0.9))
+    if divide:
+        a.divide(divide)
+    cut = rt.Cube()
+    cut.set_transform(rt.translation(-1.9, 1.3, 0.1) * rt.rotation_y(0.4) * rt.scaling(0.6, 0.6, 0.6))
+    cut.material.color = rt.Color(0.3, 0.3, 0.8)
+    w.add_object(rt.Csg(rt.Operation.Difference, a, cut))
+    # a smooth torus intersected with a sphere, under a transformed Csg
+    m = rt.Material()
+    m.color = rt.Color(0.3, 0.8, 0.5)
+    m.reflective = 0.3
+    b = _mesh_group(mesh_torus(nu, nv, True, seed + 1), m, divide)
+    ball = rt.Sphere()
+    ball.set_transform(rt.translation(0.3, 0.0, 0.0) * rt.scaling(1.15, 1.15, 1.15))
+    ball.material.color = rt.Color(0.9, 0.8, 0.2)
+    both = rt.Csg(rt.Operation.Intersection, b, ball)
+    # (small enough a move that the Csg's box, tested in the wrong space, still meets the rays, csg.rs:115-118)
+    both.set_transform(rt.translation(0.1, 0.9, 0.2) * rt.rotation_z(0.3) * rt.scaling(1.0, 0.8, 1.1))
+    w.add_object(both)
+    # a glass one
+    m = rt.Material()
+    m.color = rt.Color(0.05, 0.05, 0.1)
+    m.diffuse, m.transparency, m.reflective, m.refractive_index = 0.1, 0.9, 0.5, 1.45
+    c = _mesh_group(mesh_torus(max(3, nu // 2), max(3, nv // 2), False, seed + 2), m)
+    c.set_transform(rt.translation(2.5, 0.8, 0.4) * rt.rotation_x(-0.6) * rt.scaling(0.8, 0.8, 0.8))
+    if divide:
+        c.divide(divide)
+    hole = rt.Sphere()
+    hole.set_transform(rt.translation(3.1, 0.9, 0.0) * rt.scaling(0.6, 0.6, 0.6))
+    hole.set_material(m)
+    w.add_object(rt.Csg(rt.Operation.Difference, c, hole))
+    w.add_light(rt.PointLight(rt.Point(-6.0, 8.0, -8.0), rt.Color(0.9, 0.9, 0.9)))
+    w.add_light(rt.PointLight(rt.Point(5.0, 6.0, -3.0), rt.Color(0.35, 0.35, 0.4)))
+    return w, _camera(width, height, PI / 3.0, (0.0, 2.8, -6.5), (0.0, 0.8, 0.0)), depth
+
+
+def csg_mesh_random(seed, width=24, height=16):
+    """A seeded random scene of meshes under Csgs: a floor, two plain glass spheres, and two or three Csg
+    trees of random operations (up to 4 levels) over tetrahedra and mesh_torus(4, 3), flat and smooth, and
+    kinds 0-4; groups between the nodes, some divided; some Csgs transformed; glass and mirrors; every
+    third seed's camera sits inside the first tree."""
+    rng = SplitMix64(0xC5610000 ^ seed)
+    w = rt.World()
+    floor = rt.Plane()
+    floor.set_transform(rt.translation(0, -1.3, 0))
+    floor.material.color = rt.Color(0.7, 0.7, 0.6)
+    floor.material.reflective = 0.25 * rng.u()
+    w.add_object(floor)
+    for k in range(2):
+        s = rt.glass_sphere()
+        r = 0.3 + 0.3 * rng.u()
+        s.set_transform(rt.translation(-2.8 + 5.6 * k + 0.4 * rng.u(), -0.4 + rng.u(), 1.0 + rng.u()) * rt.scaling(r, r, r))
+        s.material.refractive_index = 1.2 + 0.6 * rng.u()
+        s.material.reflective = 0.3
+        w.add_object(s)
+
+    def mat():
+        m = rt.Material()
+        m.color = rt.Color(rng.u(), rng.u(), rng.u())
+        style = rng.u()
+        if style < 0.35:
+            m.transparency = 0.5 + 0.5 * rng.u()
+            m.refractive_index = 1.1 + 0.9 * rng.u()
+            m.reflective = 0.5 * rng.u()
+            m.diffuse = 0.3
+        elif style < 0.55:
+            m.reflective = 0.2 + 0.6 * rng.u()
+        return m
+
+    def place(cx, cz, lo=0.45, hi=0.95):
+        sc = [lo + (hi - lo) * rng.u() for _ in range(3)]
+        return (rt.translation(cx + 0.7 * (rng.u() - 0.5), 0.7 * (rng.u() - 0.5), cz + 0.7 * (rng.u() - 0.5))
+                * rt.rotation_y(PI * rng.u()) * rt.rotation_x(PI * rng.u()) * rt.scaling(*sc))
+
+    def tetra(smooth):
+        v = [(1.0 + 0.05 * rng.u(), 1.0 + 0.05 * rng.u(), 1.0 + 0.05 * rng.u()),
+             (1.0 + 0.05 * rng.u(), -1.0 - 0.05 * rng.u(), -1.0 - 0.05 * rng.u()),
+             (-1.0 - 0.05 * rng.u(), 1.0 + 0.05 * rng.u(), -1.0 - 0.05 * rng.u()),
+             (-1.0 - 0.05 * rng.u(), -1.0 - 0.05 * rng.u(), 1.0 + 0.05 * rng.u())]
+        p = [rt.Point(*q) for q in v]
+        n = [rt.Vector(*q) for q in v]
+        g = rt.Group()
+        for a, b, c in ((0, 1, 2), (0, 3, 1), (0, 2, 3), (1, 3, 2)):
+            g.add_child(rt.SmoothTriangle(p[a], p[b], p[c], n[a], n[b], n[c]) if smooth else rt.Triangle(p[a], p[b], p[c]))
+        return g
+
+    def leaf(cx, cz):
+        pick = int(rng.u() * 8)
+        if pick < 4:  # a mesh
+            smooth = pick & 1 == 1
+            g = tetra(smooth) if pick < 2 else rt.parse_obj_string(mesh_torus(4, 3, smooth, 0x5EED0000 + int(rng.u() * 1e6))).as_group()
+            g.set_material(mat())
+            g.set_transform(place(cx, cz, 0.5, 0.9))
+            if rng.u() < 0.4:
+                g.divide(2 + int(rng.u() * 3))
+            return g
+        s = (rt.Sphere(), rt.Cube(), rt.Cylinder(-1.0, 1.0, True), rt.Cone(-1.0, 0.0, True))[pick - 4]
+        s.set_transform(place(cx, cz))
+        s.set_material(mat())
+        if rng.u() < 0.15:
+            s.no_shadow()
+        return s
+
+    def tree(level, cx, cz):
+        op = (rt.Operation.Union, rt.Operation.Intersection, rt.Operation.Difference)[int(rng.u() * 3)]
+        sides = []
+        for _ in range(2):
+            side = tree(level - 1, cx, cz) if level > 1 and rng.u() < 0.55 else leaf(cx, cz)
+            if rng.u() < 0.25:  # a group between the nodes
+                g = rt.Group()
+                g.add_child(side)
+                g.add_child(leaf(cx, cz))
+                side = g
+            sides.append(side)
+        c = rt.Csg(op, sides[0], sides[1])
+        if rng.u() < 0.3:  # (a small move: the Csg's box is tested against the local ray, csg.rs:115-118)
+            c.set_transform(rt.translation(0.1 * (rng.u() - 0.5), 0.1 * (rng.u() - 0.5), 0.0) * rt.rotation_y(0.3 * (rng.u() - 0.5))
+                            * rt.scaling(0.9 + 0.2 * rng.u(), 0.9 + 0.2 * rng.u(), 0.9 + 0.2 * rng.u()))
+        return c
+
+    n_trees = 2 + int(rng.u() * 2)
+    for k in range(n_trees):
+        cx = 2.4 * (k - (n_trees - 1) / 2.0)
+        t = tree(1 + int(rng.u() * 4), cx, 0.5)
+        if k == 1:
+            g = rt.Group()
+            g.add_child(t)
+            g.add_child(leaf(cx, 2.6))
+            w.add_object(g)
+        else:
+            w.add_object(t)
+    w.add_light(rt.PointLight(rt.Point(-5, 8, -7), rt.Color(0.9, 0.9, 0.9)))
+    w.add_light(rt.PointLight(rt.Point(6, 5, -4), rt.Color(0.4, 0.4, 0.4)))
+    if seed % 3 == 2:  # from inside the first tree
+        cx = 2.4 * (0 - (n_trees - 1) / 2.0)
+        return w, _camera(width, height, 1.3, (cx + 0.05, 0.1, 0.45), (0.3, 0.2, 2.0)), 4
+    return w, _camera(width, height, PI / 3.0, (0.0, 1.5, -6.0), (0, 0.0, 0.5)), 4
