@@ -89,6 +89,7 @@ extern "C" int rtamd_wf_gen_counts(const rt_scene* s, unsigned* out, int max);
 extern "C" int rtamd_pngz_kernel_times(const double* d_rgb, uint32_t width, uint32_t height, uint8_t* d_out, size_t cap,
                                        float* ms, void* stream);
 extern "C" int rtamd_wf_plan(const rt_scene* s, long long out[16]);
+extern "C" int rtamd_wf_shape(const rt_scene* s, long long out[4]);
 extern "C" int rtamd_csg_plan(const rt_scene* s, long long out[6]);
 extern "C" int rtamd_scene_tuning_set(const rt_scene* s, const char* key, int value);
 extern "C" int rtamd_render_shard_host(const rt_scene* scene, const rt_camera_desc* camera, uint32_t max_depth,
@@ -905,6 +906,21 @@ PYBIND11_MODULE(_rtamd, m) {
     d["n_csg_units"] = o[13];
     d["n_alias_members"] = o[14];  // ... and the ALIAS kernels by (the alias classes' members; their classes)
     d["n_alias_classes"] = o[15];
+    return d;
+  }, py::arg("world"));
+  // the launch shape of the last render's fused launches: threads per block and the co-resident
+  // form that ran (the `coresident` knob; 0 = the usual shape, also where the plan fell back)
+  m.def("_wf_shape", [](const World& w) {
+    long long o[4] = {0};
+    check(rtamd_wf_shape(w.scene(), o), "wf_shape");
+    py::dict d;
+    const char* which[2] = {"primary", "secondary"};
+    for (int i = 0; i < 2; ++i) {
+      py::dict p;
+      p["threads"] = (int)o[2 * i];
+      p["coresident"] = (int)o[2 * i + 1];
+      d[which[i]] = p;
+    }
     return d;
   }, py::arg("world"));
   // the Csg units' hierarchy (unit_trace): the scene's units, those the hierarchy holds, those left

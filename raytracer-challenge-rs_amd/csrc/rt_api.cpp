@@ -155,6 +155,23 @@ int rtamd_wf_plan(const rt_scene* cs, long long out[16]) {
   return RT_OK;
 }
 
+// Development hook (not in the public ABI): the launch shape of the scene's last render's fused
+// launches (WfTuning::coresident, rt_wf_plan.hpp). out[0..1]: generation 0's threads per block and
+// co-resident form (0: the usual shape); out[2..3]: the last deeper generation's. Zeros: no such launch.
+int rtamd_wf_shape(const rt_scene* cs, long long out[4]) {
+  if (!cs || !out) return fail(RT_ERR_INVALID_ARGUMENT, "null scene or output");
+  rt_scene* s = const_cast<rt_scene*>(cs);
+  std::lock_guard<std::mutex> lk(s->mu);
+  const WfImagePlan none{};
+  const WfImagePlan* pl[2] = {s->last_wf ? &s->last_wf->wf->plan_primary() : &none,
+                              s->last_wf ? &s->last_wf->wf->plan_secondary() : &none};
+  for (int i = 0; i < 2; ++i) {
+    out[2 * i] = pl[i]->lane >= 0 ? pl[i]->threads : 0;
+    out[2 * i + 1] = pl[i]->lane >= 0 ? pl[i]->coresident : 0;
+  }
+  return RT_OK;
+}
+
 // Development hook (not in the public ABI): the Csg units' hierarchy (unit_trace). out[0..5]: the
 // scene's units, the boxed units the hierarchy holds, the units left to the loop, the hierarchy's
 // nodes and depth, and whether the last render walked it (a fused render of a scene that has one).

@@ -105,6 +105,8 @@ int render_frames(const rt_scene* scene, const rt_camera_desc* cameras, uint32_t
     job.blk_mask = blk_mask;
     if (nf > 1) job.batch = &tab;
     job.n_frames = nf;
+    // rt_render_frames_device's batches: asynchronous, and rendered with other batches in flight
+    job.in_flight = nf > 1 && blk_period == 0;
     RenderResult r;
     int rc = run_render(s, job, st, call, &r);
     if (rc != RT_OK) return rc;

@@ -40,7 +40,8 @@ int wf_tuning_apply(WfTuning& t, const char* key, int value) {
       {"d2h", &WfTuning::d2h, 0, 1},               {"bands", &WfTuning::bands, 1, 4},
       {"band_pct", &WfTuning::band_pct, 5, 95},   {"band_gen", &WfTuning::band_gen, -1, 8},
       {"band_ratio", &WfTuning::band_ratio, 30, 100}, {"multi_gather", &WfTuning::multi_gather, 0, 1},
-      {"own_sphere", &WfTuning::own_sphere, 0, 2}, {"spread", &WfTuning::spread, 0, 1}};
+      {"own_sphere", &WfTuning::own_sphere, 0, 2}, {"spread", &WfTuning::spread, 0, 1},
+      {"coresident", &WfTuning::coresident, 0, 2}};
   if (!key) return 0;
   for (const Knob& k : knobs) {
     if (std::strcmp(key, k.name) != 0) continue;
@@ -353,14 +354,21 @@ static hipError_t launch_shadow_exh(const DevScene& sc, const WfArgs& a, bool ld
 // own code object (rt_wavefront_glb.o).
 template <bool QUADS, bool TALLY, bool TRIS = false, bool CSG = false, bool ALIAS = false>
 static hipError_t launch_fused_q(const DevScene& sc, const DevCamera& cam, WfArgs a, bool primary, unsigned n,
-                                 hipStream_t stream, const WfTuning& tn, WfImagePlan* ran) {
+                                 hipStream_t stream, const WfTuning& tn, int coresident, WfImagePlan* ran) {
   // (spread: the whole grid, whatever n; the kernel deals the chunks over every block)
   if (a.spread && !tn.adaptive_block) n = 1u << 30;
-  const int tb = trace_block(n, tn.adaptive_block);
-  const WfImagePlan plan = *ran = wf_plan_image(sc, tn, primary, a.use_lb != 0);
+  // form 2 of the co-resident shape: only the plain sphere kernels have the capped twin
+  constexpr bool kCapped = !QUADS && !TALLY && !TRIS && !CSG && !ALIAS;
+  if (coresident == 2 && !kCapped) coresident = 0;
+  const WfImagePlan plan = *ran = wf_plan_image(sc, tn, primary, a.use_lb != 0, coresident);
+  const int tb = std::min(trace_block(n, tn.adaptive_block), plan.threads);
   a.lds_flags = plan.lds_flags;
   a.n_top = plan.n_top;
   const bool cam_rays = a.g == 0 && a.camera_mode;  // only generation 0 of a camera render reads camera rays
+  if constexpr (kCapped)
+    if (plan.coresident == 2)
+      return cam_rays ? launch_timed(wf_trace_fused_cap<true>, tb, plan.dyn, n, stream, sc, cam, a)
+                      : launch_timed(wf_trace_fused_cap<false>, tb, plan.dyn, n, stream, sc, cam, a);
 #define RT_LDS(P, L, C) launch_timed(wf_trace_fused<P, QUADS, L, TALLY, C, TRIS, CSG, ALIAS>, tb, plan.dyn, n, stream, sc, cam, a)
   switch (plan.lane) {
     case kLaneWave: return RT_LDS(true, kLaneWave, true);
@@ -372,23 +380,23 @@ static hipError_t launch_fused_q(const DevScene& sc, const DevCamera& cam, WfArg
   return wf_launch_global(plan.lane, QUADS, TRIS, CSG, ALIAS, TALLY, cam_rays, sc, cam, a, plan.dyn, n, stream, tb, t_ev_start, t_ev_stop);
 }
 static hipError_t launch_fused(const DevScene& sc, const DevCamera& cam, const WfArgs& a, bool primary, unsigned n,
-                               hipStream_t stream, bool tally, const WfTuning& tn, WfImagePlan* ran) {
+                               hipStream_t stream, bool tally, const WfTuning& tn, int coresident, WfImagePlan* ran) {
   // QUADS: solids outside the hierarchies, or the hierarchy over the other records
   const bool quads = sc.n_fx_quads > 0 || sc.n_obvh > 0 || sc.n_lbvh > 0;
   if (sc.n_alias_rec > 0)  // (the Csg kernels with the alias classes)
-    return tally ? launch_fused_q<true, true, true, true, true>(sc, cam, a, primary, n, stream, tn, ran)
-                 : launch_fused_q<true, false, true, true, true>(sc, cam, a, primary, n, stream, tn, ran);
+    return tally ? launch_fused_q<true, true, true, true, true>(sc, cam, a, primary, n, stream, tn, coresident, ran)
+                 : launch_fused_q<true, false, true, true, true>(sc, cam, a, primary, n, stream, tn, coresident, ran);
   if (sc.n_csg_units > 0)  // (the triangle kernels with the Csg units)
-    return tally ? launch_fused_q<true, true, true, true>(sc, cam, a, primary, n, stream, tn, ran)
-                 : launch_fused_q<true, false, true, true>(sc, cam, a, primary, n, stream, tn, ran);
+    return tally ? launch_fused_q<true, true, true, true>(sc, cam, a, primary, n, stream, tn, coresident, ran)
+                 : launch_fused_q<true, false, true, true>(sc, cam, a, primary, n, stream, tn, coresident, ran);
   if (sc.n_tris > 0)  // (their kernels are the QUADS ones with the triangle loop and walk)
-    return tally ? launch_fused_q<true, true, true>(sc, cam, a, primary, n, stream, tn, ran)
-                 : launch_fused_q<true, false, true>(sc, cam, a, primary, n, stream, tn, ran);
+    return tally ? launch_fused_q<true, true, true>(sc, cam, a, primary, n, stream, tn, coresident, ran)
+                 : launch_fused_q<true, false, true>(sc, cam, a, primary, n, stream, tn, coresident, ran);
   if (tally)
-    return quads ? launch_fused_q<true, true>(sc, cam, a, primary, n, stream, tn, ran)
-                 : launch_fused_q<false, true>(sc, cam, a, primary, n, stream, tn, ran);
-  return quads ? launch_fused_q<true, false>(sc, cam, a, primary, n, stream, tn, ran)
-               : launch_fused_q<false, false>(sc, cam, a, primary, n, stream, tn, ran);
+    return quads ? launch_fused_q<true, true>(sc, cam, a, primary, n, stream, tn, coresident, ran)
+                 : launch_fused_q<false, true>(sc, cam, a, primary, n, stream, tn, coresident, ran);
+  return quads ? launch_fused_q<true, false>(sc, cam, a, primary, n, stream, tn, coresident, ran)
+               : launch_fused_q<false, false>(sc, cam, a, primary, n, stream, tn, coresident, ran);
 }
 
 // The launch arguments every launch of a pass shares: the job's tiling and
@@ -566,6 +574,9 @@ hipError_t Wavefront::render_fast(const DevScene& sc, const WfJob& job, unsigned
   // an upper bound on any generation's rays, for the grid of the device-sized
   // launches (the kernels stride over what they find)
   const unsigned kAnyRays = 1u << 30;
+  // the co-resident shape (WfTuning::coresident) pays only beside other work: a batch whose caller
+  // keeps other passes in flight; every other render keeps the usual shape
+  const int coresident = job.in_flight && n_frames > 1 && !count ? tn.coresident : 0;
   for (unsigned g = 0; g <= max_depth; ++g) {
     a.g = g;
     a.colors = d_out;  // generation 0 without AA: the output (bind_generation keeps it)
@@ -578,7 +589,7 @@ hipError_t Wavefront::render_fast(const DevScene& sc, const WfJob& job, unsigned
     a.disc_slot = (unsigned)ccls;
     if (g == 0) prof_rays_[ccls] += n_real;
     WF_CHECK(pmark(stream, ccls, true));
-    WF_CHECK(launch_fused(sc, cam, a, prim_launch, g == 0 ? n0 : kAnyRays, stream, count, tn,
+    WF_CHECK(launch_fused(sc, cam, a, prim_launch, g == 0 ? n0 : kAnyRays, stream, count, tn, coresident,
                           g == 0 ? &plan_primary_ : &plan_secondary_));
     WF_CHECK(pmark(stream, ccls, false));
     if (job.gen_ev && (int)g == job.gen_ev_g) {
@@ -588,15 +599,24 @@ hipError_t Wavefront::render_fast(const DevScene& sc, const WfJob& job, unsigned
   }
   // combine, deepest generation first (only the nodes with children; the last
   // generation has none). Generation 0's pass records the frame's counts.
-  static int combine_grid = 0;
-  if (combine_grid == 0) combine_grid = occupancy_grid(wf_combine_parents, kWfBlock, 0, kAnyRays);
+  // In the form the pass's fused launches took (the deeper generations', which the other passes'
+  // combines meet most): one-wave blocks that fit beside a fused block of that form.
+  static int combine_grid = 0, combine_grid_co[2] = {0, 0};
+  if (combine_grid == 0) {
+    combine_grid = occupancy_grid(wf_combine_parents, kWfBlock, 0, kAnyRays);
+    combine_grid_co[0] = occupancy_grid(wf_combine_parents_co, 64, 0, kAnyRays);
+    combine_grid_co[1] = occupancy_grid(wf_combine_parents_co32, 64, 0, kAnyRays);
+  }
+  const int co_form = (max_depth > 0 ? plan_secondary_ : plan_primary_).coresident;
   for (int g = max_depth > 0 ? (int)max_depth - 1 : 0; g >= 0; --g) {
     a.g = (unsigned)g;
     a.colors = d_out;
     a.sh_cnt = shard_cnt((unsigned)g, 1);
     a.out_cnt = shard_cnt(1, 0);
     WF_CHECK(pmark(stream, WF_COMBINE, true));
-    WF_LAUNCH(wf_combine_parents, dim3(combine_grid), dim3(kWfBlock), 0, stream, sc, cam, a);
+    if (co_form == 1) WF_LAUNCH(wf_combine_parents_co, dim3(combine_grid_co[0]), dim3(64), 0, stream, sc, cam, a);
+    else if (co_form == 2) WF_LAUNCH(wf_combine_parents_co32, dim3(combine_grid_co[1]), dim3(64), 0, stream, sc, cam, a);
+    else WF_LAUNCH(wf_combine_parents, dim3(combine_grid), dim3(kWfBlock), 0, stream, sc, cam, a);
     WF_CHECK(hipGetLastError());
     WF_CHECK(pmark(stream, WF_COMBINE, false));
   }

@@ -117,6 +117,14 @@ struct WfTuning {
                            //     +4 %: the blocks then hold every CU's LDS with a few waves each), so not the default
   int own_sphere = 2;      // fast path, the shadow rays of a hit on a sphere record: 1 = from inside, test that sphere
                            //     first; 2 = also, from outside towards a light in front, leave it out (rt_trace.hpp)
+  int coresident = 2;      // fast path, batches rendered by rt_render_frames_device (passes in flight on other streams):
+                           //     the fused launches over the four-wide LDS image leave room on every CU for another
+                           //     pass's combine. 2 (default; C3 0.801 -> 0.781 ms/frame) = 16 waves of at
+                           //     most 120 registers (the plain sphere kernels only), the combine in one-wave blocks of at
+                           //     most 32; 1 = blocks of 15 waves, so one SIMD keeps 128 registers per lane free, and the
+                           //     combine in one-wave blocks of at most 64 (C3 0.814: the lost wave costs more than the
+                           //     room buys); 0 = neither. Where the plan finds no LDS left for the combine's blocks, or
+                           //     the launch's kernel has no capped twin: the usual shape
 };
 // Applies `key` = `value` to `t`: 1 = applied, 0 = not a render-time key, -1 = bad value.
 int wf_tuning_apply(WfTuning& t, const char* key, int value);
@@ -124,10 +132,14 @@ int wf_tuning_apply(WfTuning& t, const char* key, int value);
 // The scene image of one fused launch of the fast path (wf_plan_image,
 // rt_wf_plan.hpp): wf_trace_fused's LANE (-1: no fused launch), what it stages
 // in LDS (WfArgs::lds_flags, n_top) and the dynamic LDS it asks for.
+// `threads`: the launch's block (kTraceBlock, or kTraceBlockCo with `coresident` = 1);
+// `coresident`: the form of WfTuning::coresident the launch runs in (0: the usual shape).
 struct WfImagePlan {
   int lane = -1;
   unsigned lds_flags = 0, n_top = 0;
   size_t dyn = 0;
+  int threads = 0;
+  int coresident = 0;
 };
 
 // The fast path's launch over a global-memory scene image (lane 4, 3 or 1) of
@@ -344,6 +356,9 @@ struct WfJob {
   // generations run); Wavefront::gen_event_recorded() tells whether it did
   hipEvent_t gen_ev = nullptr;
   int gen_ev_g = -1;
+  // the caller keeps other passes in flight on other streams (rt_render_frames_device's batches):
+  // the pass may take the co-resident launch shape (WfTuning::coresident)
+  bool in_flight = false;
 
   bool camera_mode() const { return d_in_rays == nullptr; }
   static WfJob camera_shard(const DevCamera& cam, unsigned n0, unsigned aa, unsigned max_depth, double* d_out,

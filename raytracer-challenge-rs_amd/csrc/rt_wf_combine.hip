@@ -172,9 +172,8 @@ __device__ __forceinline__ void poison_frames(const WfArgs& a, double* single, u
   }
 }
 
-__global__ __launch_bounds__(kWfBlock) void wf_combine_parents(DevScene sc, DevCamera cam, WfArgs a) {
+__device__ __forceinline__ void combine_parents(const DevScene& sc, const DevCamera& cam, WfArgs a, unsigned* s_pre) {
   const unsigned stride = gridDim.x * blockDim.x;
-  __shared__ unsigned s_pre[kPreList];
   const unsigned* pre = shard_prefix<false>(a.sh_cnt, s_pre);
   const WfGenTab t = a.gtab[a.g];
   const unsigned sh_cap = a.gsh[a.g];
@@ -222,6 +221,28 @@ __global__ __launch_bounds__(kWfBlock) void wf_combine_parents(DevScene sc, DevC
     double* out = color_dst(a, cam, p.slot);
     out[0] = col.x; out[1] = col.y; out[2] = col.z;
   }
+}
+
+__global__ __launch_bounds__(kWfBlock) void wf_combine_parents(DevScene sc, DevCamera cam, WfArgs a) {
+  __shared__ unsigned s_pre[kPreList];
+  combine_parents(sc, cam, a, s_pre);
+}
+// The co-resident forms (WfTuning::coresident, rt_wf_plan.hpp): the same pass in one-wave blocks,
+// each of which needs one wave slot on one SIMD, few enough registers to fit what a fused block of
+// the co-resident shape leaves free there (64: two waves in form 1's 128; 32: one in form 2's 32)
+// and kCombineStaticLds of the LDS the plan kept for them. Same arithmetic, same order; the grid
+// is still what the device holds when the launch runs alone (a grid-stride loop).
+static_assert(sizeof(unsigned) * kPreList == kCombineStaticLds, "the plan's LDS condition counts s_pre");
+__global__ __launch_bounds__(64, 8) void wf_combine_parents_co(DevScene sc, DevCamera cam, WfArgs a) {
+  __shared__ unsigned s_pre[kPreList];
+  combine_parents(sc, cam, a, s_pre);
+}
+// (the attribute counts registers of one of the unified file's two halves: 16 bounds the wave's 32)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(16))) void wf_combine_parents_co32(DevScene sc,
+                                                                                                    DevCamera cam,
+                                                                                                    WfArgs a) {
+  __shared__ unsigned s_pre[kPreList];
+  combine_parents(sc, cam, a, s_pre);
 }
 
 // Color::average (color.rs:26-33) of the AA samples of each pixel: a left

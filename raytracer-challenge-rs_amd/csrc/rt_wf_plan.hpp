@@ -1,6 +1,7 @@
 // rt_wf_plan.hpp — which scene image a fused launch of the fast path runs over
-// (wf_trace_fused's LANE) and how its block's dynamic LDS is laid out. The
-// host takes both from here (launch_fused_q asks for WfImagePlan::dyn bytes),
+// (wf_trace_fused's LANE), how its block's dynamic LDS is laid out, and the
+// launch's shape (threads per block, the co-resident form). The host takes
+// them from here (launch_fused_q asks for WfImagePlan::dyn bytes and threads),
 // and so does the kernel: each image's stage (rt_trace.hpp LaneImage) takes its
 // region offsets from lane_lds_layout; tests/cpp/plan_check.cpp holds the bytes
 // a stage writes into a region to the region's size.
@@ -19,6 +20,26 @@ namespace rtamd {
 constexpr int kTraceBlock = 1024;  // trace kernels: 16 waves, one LDS image per block
 // LDS a fused trace launch may take (of the CU's 160 KB)
 constexpr size_t kFusedLdsLimit = 160 * 1024 - 1024;
+
+// The co-resident launch shape (WfTuning::coresident). A fused block over an LDS
+// image holds its CU's LDS, and its 16 waves of up to 128 registers every SIMD's register file,
+// so no wave of another pass's combine fits beside it. Form 1 launches blocks of kTraceBlockCo
+// threads: 15 waves, one SIMD of each CU at three, 128 registers per lane free there for
+// kCoBlocksA one-wave combine blocks of at most 64. Form 2 keeps 16 waves of at most
+// kCoCapVgprs registers, 32 free on every SIMD for kCoBlocksB combine blocks of at most 32.
+// The LDS stacks keep their kTraceBlock stride either way (a block of fewer threads leaves
+// the last columns unused), so lane_lds_layout does not depend on the form.
+constexpr int kTraceBlockCo = kTraceBlock - 64;
+constexpr int kCoBlocksA = 2, kCoBlocksB = 4, kCoCapVgprs = 120;
+constexpr size_t kCuLdsBytes = 160 * 1024;
+constexpr size_t kFusedPrefixLds = 528;    // wf_trace_fused's s_pre (and stack_lds's placeholder), as reported
+constexpr size_t kCombineStaticLds = 260;  // wf_combine_parents' s_pre[kPreList]
+// What a block's LDS takes of the CU's: whole allocation units. gfx950 hands its 160 KiB out
+// in units of 320 words; the 128-word unit of the smaller LDS is held too.
+constexpr size_t lds_alloc_bytes(size_t b) {
+  const size_t u = (b + 1279) / 1280 * 1280, v = (b + 511) / 512 * 512;
+  return u > v ? u : v;
+}
 
 // wf_trace_fused's LANE (the values are the template arguments):
 constexpr int kLaneWave = 0;      // wave traversal for primary rays (shared-origin records)
@@ -128,7 +149,19 @@ inline size_t pair_image_leaf_estimate(int bvh_depth, size_t n_nodes, size_t n_d
 // class 0.128 -> 0.125 ms/frame with the LDS four-wide image; C5's global
 // image: 2.06 -> 2.16 ms with binary32 nodes, 2.17 -> 2.01 ms with the
 // binary16 ones), 2 = over the LDS images only.
-inline WfImagePlan wf_plan_image(const DevScene& sc, const WfTuning& tn, bool primary, bool use_lb) {
+//
+// `coresident`: the form the launch may take (the caller's: WfTuning::coresident for a pass with
+// others in flight, and for form 2 only where the launch's kernel has the capped twin; else 0).
+// The plan grants it to the four-wide LDS image (kLaneWideLds, the image the shape was measured
+// on) when the CU's LDS still holds the combine's blocks beside the fused block:
+//   alloc(dyn + static) + blocks x alloc(the combine's static) <= 160 KiB
+// and falls back to the usual shape (threads = kTraceBlock, coresident = 0) otherwise.
+constexpr bool coresident_lds_fits(int lane, size_t dyn, int blocks) {
+  return lds_alloc_bytes(dyn + lane_static_lds_bytes(lane) + kFusedPrefixLds) +
+             (size_t)blocks * lds_alloc_bytes(kCombineStaticLds) <= kCuLdsBytes;
+}
+inline WfImagePlan wf_plan_image(const DevScene& sc, const WfTuning& tn, bool primary, bool use_lb,
+                                 int coresident = 0) {
   const size_t dl = use_lb ? delta_lds_bytes(sc) : 0;
   const bool wide_ok = tn.image != 1 && tn.wide && sc.bvhw16 && wide_stack_bytes(sc) <= kFusedLdsLimit / 2;
   const bool wide_lds = tn.image == 0 && sc.bvhw && tn.lds_wide && wide_lds_bytes(sc) + dl <= kFusedLdsLimit;
@@ -152,6 +185,13 @@ inline WfImagePlan wf_plan_image(const DevScene& sc, const WfTuning& tn, bool pr
     p.n_top = (unsigned)std::min<size_t>(n_nodes, (room - used()) / 64);  // BvhNode and BvhWide16: 64 B
   }
   p.dyn = used();
+  p.threads = kTraceBlock;
+  if (p.lane == kLaneWideLds && coresident == 1 && coresident_lds_fits(p.lane, p.dyn, kCoBlocksA)) {
+    p.threads = kTraceBlockCo;
+    p.coresident = 1;
+  } else if (p.lane == kLaneWideLds && coresident == 2 && coresident_lds_fits(p.lane, p.dyn, kCoBlocksB)) {
+    p.coresident = 2;
+  }
   return p;
 }
 static_assert(sizeof(BvhNode) == 64 && sizeof(BvhWide16) == 64, "wf_plan_image: a treelet node is 64 B");
