@@ -163,6 +163,15 @@ typedef struct rt_node_desc {
 #define RT_CSG_MAX_LEAVES 16
 #define RT_CSG_MAX_DEPTH 4
 #define RT_CSG_MAX_NODES 32
+/* What remains with RT_SCENE_DEEP_CSG (rt_scene_create_ex), per Csg that has no
+ * Csg above it: the limits of its record formats. RT_CSG_DEEP_MAX_NODES Csg
+ * nodes below and including it and RT_CSG_DEEP_MAX_LEAVES primitives of kinds
+ * Sphere .. Cone (the 15 + 16 bits of a batch entry's tag),
+ * RT_CSG_DEEP_MAX_LEVELS Csg nodes on any path down from it (each open level
+ * holds its ray, 48 bytes per lane of a launch). */
+#define RT_CSG_DEEP_MAX_NODES 32768
+#define RT_CSG_DEEP_MAX_LEAVES 65536
+#define RT_CSG_DEEP_MAX_LEVELS 1024
 
 /* The vertices of a `Triangle` (triangle.rs:24-44) or `SmoothTriangle`
  * (smooth_triangle.rs:27-55) in object space; its rt_shape_desc carries the
@@ -297,7 +306,8 @@ int rt_scene_create_mesh(const rt_shape_desc* shapes, size_t n_shapes,
  * Group, as a mesh is); more than RT_CSG_MAX_LEAVES primitives of kinds
  * Sphere .. Cone under one outermost Csg; more than RT_CSG_MAX_DEPTH nested
  * Csgs; more than RT_CSG_MAX_NODES Csg nodes in an outermost Csg with a
- * triangle below it. The message names the cap.
+ * triangle below it. The message names the cap. (rt_scene_create_ex with
+ * RT_SCENE_DEEP_CSG lifts these three caps.)
  * RT_ERR_DUPLICATE_SHAPES: as the other entry points, two shapes that may be
  * structurally equal, two triangles under a Csg included. */
 int rt_scene_create_tree(const rt_shape_desc* shapes, size_t n_shapes,
@@ -339,6 +349,45 @@ int rt_scene_create_aliased(const rt_shape_desc* shapes, size_t n_shapes,
                             const rt_light_desc* lights, size_t n_lights,
                             const int32_t* equal_pairs, size_t n_pairs, int device,
                             rt_scene** out);
+/* (ABI 6, additive) Every rt_scene_create* above through one call, with
+ * opt-ins: rt_scene_create_aliased's parameters in its order through n_pairs,
+ * then `flags`, a bitwise OR of
+ *   RT_SCENE_ALIASED   rt_scene_create_aliased (the equal pairs are read);
+ *   RT_SCENE_DEEP_CSG  Csg trees of any depth and leaf count: the three caps
+ *                      RT_CSG_MAX_LEAVES, RT_CSG_MAX_DEPTH and RT_CSG_MAX_NODES
+ *                      are lifted, and nothing else changes.
+ * With flags 0 this is rt_scene_create_tree (equal_pairs must be NULL and
+ * n_pairs 0); RT_ERR_INVALID_ARGUMENT for an unknown bit, and for pairs
+ * without RT_SCENE_ALIASED.
+ * With RT_SCENE_DEEP_CSG an outermost Csg within all three caps is held and
+ * evaluated exactly as without the flag (same records, same culling
+ * hierarchy). One beyond a cap is a DEEP unit: the same stream of roots in
+ * ascending (t, key), in batches of 64, through one "inside left" and one
+ * "inside right" bit per Csg node, with state that grows with the unit. That
+ * state (2 bits per Csg node, 1 per primitive of kinds Sphere .. Cone and 48
+ * bytes per level, for the scene's largest deep unit) lives in device memory
+ * per lane of a launch: each render workspace of such a scene holds it for
+ * every thread the device runs at once, each rt_hit_batch /
+ * rt_is_shadowed_batch call for its rays. It is allocated at the first render
+ * or batch call; when it cannot be, that call fails with RT_ERR_HIP and a
+ * message that names the bytes asked for. A scene without a deep unit
+ * allocates nothing. A deep unit has no culling box: it is kept out of the
+ * Csgs' hierarchy, and every ray that meets the reference's own Csg box
+ * evaluates it (cost linear in its leaves per 64 roots).
+ * Still RT_ERR_UNSUPPORTED_SHAPE, with rt_scene_create_tree's messages: a lone
+ * Triangle / SmoothTriangle as a Csg's own child; more triangles and solids
+ * under one Csg than the gates' counter holds (4194303). And the format limits
+ * RT_CSG_DEEP_MAX_NODES, RT_CSG_DEEP_MAX_LEAVES and RT_CSG_DEEP_MAX_LEVELS (the
+ * message names the limit). Still RT_ERR_DUPLICATE_SHAPES: an aliased
+ * primitive under a Csg; duplicates without RT_SCENE_ALIASED. */
+enum { RT_SCENE_ALIASED = 1, RT_SCENE_DEEP_CSG = 2 };
+int rt_scene_create_ex(const rt_shape_desc* shapes, size_t n_shapes,
+                       const int32_t* shape_node, const int32_t* shape_side,
+                       const rt_node_desc* nodes, size_t n_nodes,
+                       const rt_triangle_desc* tris, size_t n_tris,
+                       const rt_light_desc* lights, size_t n_lights,
+                       const int32_t* equal_pairs, size_t n_pairs, uint32_t flags,
+                       int device, rt_scene** out);
 /* (ABI 6, additive) The pairs rt_scene_create_aliased takes, for shapes of
  * kinds Sphere .. Cone built the way the reference's constructors followed by
  * at most ONE set_transform build them (a bitwise-identity `transform` stands

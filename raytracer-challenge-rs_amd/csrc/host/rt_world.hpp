@@ -682,20 +682,30 @@ class World {
       const Flat f = flatten();
       auto l = light_descs();
       rt_scene* s = nullptr;
+      std::vector<int32_t> pairs;
+      size_t n_pairs = 0;
       if (aliases_) {
         // The pairs of structurally equal primitives. rt_shapes_equal_pairs assumes shapes built by
         // their constructor and at most one set_transform; that is the caller's to meet (this mirror
         // does not count the calls: a shape transformed twice may compare otherwise in the reference).
         // Room for one pair a shape, which exact and near duplicates rarely pass: one sweep, not two.
-        size_t n_pairs = 0;
-        std::vector<int32_t> pairs(2 * f.shapes.size());
+        pairs.resize(2 * f.shapes.size());
         int rc = rt_shapes_equal_pairs(f.shapes.data(), f.shapes.size(), pairs.data(), f.shapes.size(), &n_pairs);
         if (rc == RT_ERR_BUFFER_TOO_SMALL) {
           pairs.resize(2 * n_pairs);
           rc = rt_shapes_equal_pairs(f.shapes.data(), f.shapes.size(), pairs.data(), n_pairs, &n_pairs);
         }
         check(rc, "rt_shapes_equal_pairs");
-        // (`nodes` holds the groups without a Csg too)
+      }
+      // (`nodes` holds the groups without a Csg too)
+      if (deep_csg_) {
+        // rt_scene_create_ex: Csg trees beyond the caps (RT_SCENE_DEEP_CSG), with the equal pairs when opted in
+        check(rt_scene_create_ex(f.shapes.data(), f.shapes.size(), f.shape_group.data(), f.shape_side.data(),
+                                 f.nodes.data(), f.nodes.size(), f.tris.data(), f.tris.size(), l.data(), l.size(),
+                                 aliases_ ? pairs.data() : nullptr, aliases_ ? n_pairs : 0,
+                                 (uint32_t)RT_SCENE_DEEP_CSG | (aliases_ ? (uint32_t)RT_SCENE_ALIASED : 0u), device, &s),
+              "rt_scene_create_ex");
+      } else if (aliases_) {
         check(rt_scene_create_aliased(f.shapes.data(), f.shapes.size(), f.shape_group.data(), f.shape_side.data(),
                                       f.nodes.data(), f.nodes.size(), f.tris.data(), f.tris.size(), l.data(), l.size(),
                                       pairs.data(), n_pairs, device, &s),
@@ -722,11 +732,24 @@ class World {
     aliases_ = on;
   }
   bool aliases() const { return aliases_; }
+  // Opt-in (off by default: a Csg tree beyond RT_CSG_MAX_DEPTH, RT_CSG_MAX_LEAVES or RT_CSG_MAX_NODES is
+  // refused): upload through rt_scene_create_ex with RT_SCENE_DEEP_CSG, which renders trees of any
+  // depth and leaf count. Sticky, as the aliases; changing it drops the uploaded scene.
+  void set_deep_csg(bool on) {
+    if (on != deep_csg_) drop();
+    deep_csg_ = on;
+  }
+  bool deep_csg() const { return deep_csg_; }
   // upload(device) keeps the opt-in as it is (a world from the scene parser stays opted in when it
   // moves to another device); upload(device, aliases) sets it.
   void upload(int device = 0) { scene(device); }
   void upload(int device, bool aliases) {
     set_aliases(aliases);
+    scene(device);
+  }
+  void upload(int device, bool aliases, bool deep_csg) {
+    set_aliases(aliases);
+    set_deep_csg(deep_csg);
     scene(device);
   }
   int scene_device() const { return scene_ ? scene_device_ : -1; }
@@ -762,6 +785,7 @@ class World {
   mutable rt_scene* scene_ = nullptr;
   mutable int scene_device_ = -1;
   bool aliases_ = false;
+  bool deep_csg_ = false;
 };
 
 // camera.rs:220-253

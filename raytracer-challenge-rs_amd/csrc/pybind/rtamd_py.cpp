@@ -91,6 +91,7 @@ extern "C" int rtamd_pngz_kernel_times(const double* d_rgb, uint32_t width, uint
 extern "C" int rtamd_wf_plan(const rt_scene* s, long long out[16]);
 extern "C" int rtamd_wf_shape(const rt_scene* s, long long out[4]);
 extern "C" int rtamd_csg_plan(const rt_scene* s, long long out[6]);
+extern "C" int rtamd_csg_deep_plan(const rt_scene* s, long long out[5]);
 extern "C" int rtamd_scene_tuning_set(const rt_scene* s, const char* key, int value);
 extern "C" int rtamd_render_shard_host(const rt_scene* scene, const rt_camera_desc* camera, uint32_t max_depth,
                                        uint32_t aa_samples, uint32_t row_block, uint32_t shard, uint32_t n_shards,
@@ -508,11 +509,15 @@ PYBIND11_MODULE(_rtamd, m) {
       // (rt_shapes_equal_pairs + rt_scene_create_aliased); the default refuses them
       // aliases=None (the default) leaves the world's opt-in as it is: off for a new World, on for one
       // the scene parser built, and what an earlier upload(aliases=...) set
-      .def("upload", [](World& w, int device, py::object aliases) {
-        if (aliases.is_none()) w.upload(device);
-        else w.upload(device, aliases.cast<bool>());
-      }, py::arg("device") = 0, py::arg("aliases") = py::none())
+      // deep_csg=True: Csg trees beyond the caps (rt_scene_create_ex, RT_SCENE_DEEP_CSG); None leaves
+      // the opt-in as it is, as aliases
+      .def("upload", [](World& w, int device, py::object aliases, py::object deep_csg) {
+        if (!aliases.is_none()) w.set_aliases(aliases.cast<bool>());
+        if (!deep_csg.is_none()) w.set_deep_csg(deep_csg.cast<bool>());
+        w.upload(device);
+      }, py::arg("device") = 0, py::arg("aliases") = py::none(), py::arg("deep_csg") = py::none())
       .def_property_readonly("aliases", &World::aliases)
+      .def_property_readonly("deep_csg", &World::deep_csg)
       .def_property_readonly("scene_device", &World::scene_device)  // -1: not uploaded
       .def("_scene_handle", [](const World& w) { return (uintptr_t)w.scene_handle(); })
       .def("_debug_relabel_device", &World::debug_relabel_device)
@@ -931,6 +936,15 @@ PYBIND11_MODULE(_rtamd, m) {
     py::dict d;
     d["units"] = o[0]; d["records"] = o[1]; d["remainder"] = o[2];
     d["nodes"] = o[3]; d["depth"] = o[4]; d["ran"] = o[5] != 0;
+    return d;
+  }, py::arg("world"));
+  // the deep Csg units (csg_deep_eval): how many, the largest one's levels, Csg nodes and leaves of
+  // kinds 0-4, and the bytes of deep state per lane of a launch
+  m.def("_csg_deep_plan", [](const World& w) {
+    long long o[5] = {0};
+    check(rtamd_csg_deep_plan(w.scene(), o), "csg_deep_plan");
+    py::dict d;
+    d["units"] = o[0]; d["levels"] = o[1]; d["nodes"] = o[2]; d["leaves"] = o[3]; d["lane_bytes"] = o[4];
     return d;
   }, py::arg("world"));
   m.def("_tuning_set", [](const std::string& k, int v) { check(rtamd_tuning_set(k.c_str(), v), "tuning"); });

@@ -22,6 +22,8 @@ int g_csg_hier_min = kCsgHierMinDefault;
 // every Csg unit through the wide units' streamed evaluator, out of the units' hierarchy
 // ("csg_wide_all": the cross-check of csg_wide_eval against csg_unit_eval; off by default)
 int g_csg_wide_all = 0;
+// ("csg_deep_all": the same cross-check of csg_deep_eval against the other two)
+int g_csg_deep_all = 0;
 std::mutex g_tune_mu;
 WfTuning g_tune_defaults;
 
@@ -190,6 +192,16 @@ int rtamd_csg_plan(const rt_scene* cs, long long out[6]) {
   return RT_OK;
 }
 
+// Development hook (not in the public ABI): the deep Csg units (csg_deep_eval). out[0..4]: the
+// scene's deep units, the largest one's levels, Csg nodes and leaves of kinds 0-4 (each the
+// greatest over the deep units), and the bytes of deep state a lane of a launch holds.
+int rtamd_csg_deep_plan(const rt_scene* cs, long long out[5]) {
+  if (!cs || !out) return fail(RT_ERR_INVALID_ARGUMENT, "null scene or output");
+  for (int k = 0; k < 4; ++k) out[k] = cs->csg_deep_plan[k];
+  out[4] = 4ll * csg_deep_words((int32_t)out[2], (int32_t)out[3], (int32_t)out[1]) * (out[0] ? 1 : 0);
+  return RT_OK;
+}
+
 // Rays of each generation of the scene's last render (dev tool): returns the
 // number of generations written into out[0 .. max).
 int rtamd_wf_gen_counts(const rt_scene* cs, unsigned* out, int max) {
@@ -235,6 +247,11 @@ int rtamd_tuning_set(const char* key, int value) {
   if (key && std::strcmp(key, "csg_wide_all") == 0) {
     if (value < 0 || value > 1) return fail(RT_ERR_INVALID_ARGUMENT, "csg_wide_all must be 0 or 1");
     g_csg_wide_all = value;
+    return RT_OK;
+  }
+  if (key && std::strcmp(key, "csg_deep_all") == 0) {
+    if (value < 0 || value > 1) return fail(RT_ERR_INVALID_ARGUMENT, "csg_deep_all must be 0 or 1");
+    g_csg_deep_all = value;
     return RT_OK;
   }
   std::lock_guard<std::mutex> lk(g_tune_mu);

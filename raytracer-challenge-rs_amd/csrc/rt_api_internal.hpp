@@ -52,6 +52,7 @@ extern int g_bvh_ct;    // SAH node-visit cost in percent of a sphere test
 extern int g_lb_res;    // light-buffer cells per cube-map face edge: 0 = none, -1 = by scene size
 extern int g_csg_hier_min;  // boxed Csg units from which their hierarchy is built
 extern int g_csg_wide_all;  // every Csg unit through the wide units' evaluator (development cross-check)
+extern int g_csg_deep_all;  // every Csg unit through the deep units' evaluator (the same; it wins over csg_wide_all)
 // render-time tuning copied into every scene at its creation (rt_scene::tune)
 extern std::mutex g_tune_mu;
 extern WfTuning g_tune_defaults;
@@ -154,6 +155,8 @@ struct rt_scene {
     hipStream_t band_stream[kMaxBands - 1] = {};
     hipEvent_t band_ev[kMaxBands] = {};
     unsigned long long* h_len = nullptr;  // rt_render_ppm: the text's length (a pinned word)
+    uint32_t* d_deep = nullptr;  // rt_hit_batch / rt_is_shadowed_batch of a scene with a deep Csg unit: the lanes' state
+    size_t deep_cap = 0;         // words
     bool busy = false;
   };
   std::deque<HostCtx> ctxs;  // deque: a context's address survives the pool's growth
@@ -206,6 +209,7 @@ struct rt_scene {
   std::mutex multi_mu;
   int prof_mask = (1 << WF_NCLASS) - 1;
   int n_objects = 0, n_lights = 0;
+  long long csg_deep_plan[4] = {0, 0, 0, 0};  // deep Csg units; the largest one's levels, nodes, leaves of kinds 0-4
   WfTuning tune;  // this scene's render-time tuning (read under `mu` by every render)
   WfSizing sizing;  // the fast path's queue arenas, learned from this scene's frames (under `mu`)
   // ... and from the row bands of rt_render (render_banded): a band's rays per root ray
@@ -221,7 +225,7 @@ struct rt_scene {
         (void)hipStreamDestroy(c.stream);
       }
       (void)hipFree(c.d_out); (void)hipFree(c.d_in); (void)hipFree(c.d_ppm); (void)hipFree(c.d_ppm_rows);
-      (void)hipFree(c.d_png); (void)hipFree(c.d_pngz);
+      (void)hipFree(c.d_png); (void)hipFree(c.d_pngz); (void)hipFree(c.d_deep);
       for (int k = 0; k < 2; ++k) {
         if (c.h_stage[k]) (void)hipHostFree(c.h_stage[k]);
         if (c.stage_ev[k]) (void)hipEventDestroy(c.stage_ev[k]);
@@ -292,6 +296,9 @@ namespace rtapi __attribute__((visibility("hidden"))) {
 
 // ---- rt_workspace.cpp
 int ensure_dev_buffer(double** buf, size_t* cap, size_t need);
+// The scene for a batch launch of n lanes from context `c`: the scene's own, with the context's
+// deep-Csg state buffer (grown to n lanes) when the scene has a deep unit.
+int batch_scene(const rt_scene* s, rt_scene::HostCtx* c, size_t n, DevScene* out);
 // Device-to-host copy of n bytes into caller memory, stream-ordered after the
 // work already on `st`; synchronous.
 int copy_to_host(rt_scene::HostCtx* s, int d2h, void* dst, const void* src, size_t n, hipStream_t st);

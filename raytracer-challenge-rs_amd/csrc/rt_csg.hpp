@@ -113,10 +113,12 @@ constexpr int kCsgMaxNodes = 32;  // Csg nodes in one wide unit
 // < kCsgMaxNodes), and the leaf's place in the fold's table: its number among the unit's
 // leaves of kinds 0-4 (< kCsgMaxLeaves), or kCsgTagTri for a triangle (one root, no place).
 constexpr int kCsgTagNode = 31, kCsgTagSlotShift = 5, kCsgTagSlot = 15, kCsgTagTri = 1 << 9;
-struct CsgBatch {
+template <typename Tag>
+struct CsgBatchT {
   CsgList xs;
-  uint16_t tag[kCsgListCap];
+  Tag tag[kCsgListCap];
 };
+typedef CsgBatchT<uint16_t> CsgBatch;
 
 RT_CSG_FN bool csg_above(double t, int32_t key, double wt, int32_t wk) { return t > wt || (t == wt && key > wk); }
 
@@ -124,7 +126,8 @@ RT_CSG_FN bool csg_above(double t, int32_t key, double wt, int32_t wk) { return 
 // kept ascending by insertion; `more`: a root above the watermark was left out (walk
 // again from the batch's last entry). A NaN t is above no watermark (the reference's
 // sort panics on one).
-RT_CSG_FN void csg_batch_insert(CsgBatch& b, int cap, double t, int32_t key, uint16_t tag, double wt, int32_t wk,
+template <typename Tag>
+RT_CSG_FN void csg_batch_insert(CsgBatchT<Tag>& b, int cap, double t, int32_t key, Tag tag, double wt, int32_t wk,
                                 bool& more) {
   if (!csg_above(t, key, wt, wk)) return;
   CsgList& xs = b.xs;
@@ -176,6 +179,109 @@ RT_CSG_FN void csg_neg_note(CsgNegTable& nt, int slot, double t, int32_t key) {
   nt.t[slot] = t;
   nt.key[slot] = key;
   nt.odd ^= 1u << slot;
+}
+
+// ---- The same stream for a DEEP unit (rt_layout.hpp kCsgDeep): one of any depth, node and
+// leaf count. Nothing in the argument above depends on them; only the state does. Here it
+// scales: the filter bits are bitsets of `nw` words each, the leaves' parities one of `lw`
+// words, all in the launch's state buffer (`W`: word i of this lane), and the containers need
+// no per-leaf table (csg_deep_note).
+//
+// The tag: the innermost Csg node above the leaf (15 bits), the leaf's number among the unit's
+// leaves of kinds 0-4 (16 bits), or kCsgDeepTagTri for a triangle.
+constexpr uint32_t kCsgDeepTagNode = (uint32_t)kCsgDeepMaxNodes - 1, kCsgDeepTagSlot = (uint32_t)kCsgDeepMaxLeaves - 1;
+constexpr uint32_t kCsgDeepTagTri = 1u << 31;
+constexpr int kCsgDeepTagSlotShift = 15;
+typedef CsgBatchT<uint32_t> CsgDeepBatch;
+
+// One lane's words of the state buffer (rt_layout.hpp csg_deep_words).
+struct CsgDeepWords {
+  uint32_t* w;
+  size_t stride;
+  RT_CSG_FN uint32_t& operator[](int i) const { return w[(size_t)i * stride]; }
+};
+
+// csg_stream_pass over the bitsets: inl at words [0, nw), inr at [nw, 2 nw).
+RT_CSG_FN bool csg_deep_pass(const CsgRec* nodes, int node, int32_t key, const CsgDeepWords& st, int nw) {
+  const int32_t obj = key >> kKeyShift;
+  for (int g = node; g >= 0; g = nodes[g].parent) {
+    const uint32_t bit = 1u << (g & 31);
+    const int wl = g >> 5, wr = nw + (g >> 5);
+    const uint32_t l = st[wl], r = st[wr];
+    const bool lhit = obj < nodes[g].split;
+    const bool ok = csg_allowed(nodes[g].op, lhit, (l & bit) != 0, (r & bit) != 0);
+    if (lhit) st[wl] = l ^ bit;
+    else st[wr] = r ^ bit;
+    if (!ok) return false;
+  }
+  return true;
+}
+
+// The unit's closest survivor so far, as the caller's Hit holds it.
+struct CsgDeepHit {
+  double t;
+  int32_t key;
+  int hin;
+};
+// The first pass: one entry of the ascending stream. The parity bits (words [2 nw, 2 nw + lw))
+// toggle at each survivor t < 0 of a leaf of kinds 0-4; when a survivor t >= 0 arrives all of its
+// leaf's survivors t < 0 have passed, so its bit is `hin`. `eligible(key)`: the leaf may be the
+// hit (a shadow ray's: it casts one). Returns kCsgDeepDone at the unit's hit or at the first
+// entry beyond h.t (nothing later is a hit, a container or `hin`), kCsgDeepTriNeg for a
+// triangle's surviving root t < 0 (one root a leaf: the caller's container at once).
+enum { kCsgDeepGoOn = 0, kCsgDeepDone = 1, kCsgDeepTriNeg = 2 };
+template <typename Eligible>
+RT_CSG_FN int csg_deep_step(const CsgRec* nodes, const CsgDeepWords& st, int nw, double t, int32_t key, uint32_t tag,
+                            Eligible eligible, CsgDeepHit& h) {
+  if (t > h.t) return kCsgDeepDone;
+  if (!csg_deep_pass(nodes, (int)(tag & kCsgDeepTagNode), key, st, nw)) return kCsgDeepGoOn;
+  const bool tri = (tag & kCsgDeepTagTri) != 0;
+  const int slot = (int)((tag >> kCsgDeepTagSlotShift) & kCsgDeepTagSlot);
+  if (t < 0.0) {
+    if (tri) return kCsgDeepTriNeg;
+    st[2 * nw + (slot >> 5)] ^= 1u << (slot & 31);
+    return kCsgDeepGoOn;
+  }
+  if (!eligible(key)) return kCsgDeepGoOn;
+  if (t < h.t || (t == h.t && key < h.key)) {
+    h.t = t;
+    h.key = key;
+    h.hin = tri ? 0 : (int)((st[2 * nw + (slot >> 5)] >> (slot & 31)) & 1u);
+  }
+  return kCsgDeepDone;
+}
+
+// The second pass, over the part t < 0 of the same stream with fresh filter bits, when the first
+// left a leaf odd: the caller's `containers` walk (push_container) needs of the unit only, among
+// the leaves with an odd number of survivors t < 0, the two whose LAST such survivor is greatest
+// by (t, key). The parities are final now, so a survivor of an odd leaf is a candidate as it
+// arrives: c1 is the latest of them, c2 the latest one of a DIFFERENT leaf than c1's. A survivor
+// of c1's leaf replaces c1; one of another leaf moves c1 to c2 and takes c1: the entry before a
+// new c1 is the latest survivor of every other leaf. At the end c1 is the greatest last survivor
+// and c2 the greatest among the other leaves'.
+struct CsgDeepTop2 {
+  double t1, t2;
+  int32_t k1, k2;
+  int32_t slot1;  // c1's leaf, -1: none yet
+};
+RT_CSG_FN void csg_deep_top2_init(CsgDeepTop2& c) {
+  c.k1 = c.k2 = -1;
+  c.slot1 = -1;
+  c.t1 = c.t2 = 0.0;
+}
+RT_CSG_FN void csg_deep_note(const CsgRec* nodes, const CsgDeepWords& st, int nw, double t, int32_t key, uint32_t tag,
+                             CsgDeepTop2& c) {
+  if (!csg_deep_pass(nodes, (int)(tag & kCsgDeepTagNode), key, st, nw)) return;
+  if (tag & kCsgDeepTagTri) return;  // (the first pass pushed it)
+  const int slot = (int)((tag >> kCsgDeepTagSlotShift) & kCsgDeepTagSlot);
+  if (!((st[2 * nw + (slot >> 5)] >> (slot & 31)) & 1u)) return;
+  if (slot != c.slot1) {
+    c.t2 = c.t1;
+    c.k2 = c.k1;
+    c.slot1 = slot;
+  }
+  c.t1 = t;
+  c.k1 = key;
 }
 
 }  // namespace rtamd

@@ -622,23 +622,158 @@ __device__ __forceinline__ void csg_wide_eval(const DevScene& sc, const CsgUnit 
     for (int s = 0; s < kCsgMaxLeaves; ++s)
       if ((nt.odd >> s) & 1u) push_container(h, nt.t[s], nt.key[s]);
 }
+// The same for a DEEP unit (rt_layout.hpp kCsgDeep: any depth, node and leaf count), the stream
+// form again: csg_wide_eval's walk, gates, chained ray, batches and stop, with state that scales
+// (rt_csg.hpp csg_deep_step / csg_deep_note). The filter bits, the leaves' parity bits and the
+// ray each open level's Enter found live in the launch's state buffer, this lane's words
+// (DevScene::csg_deep_state: no scratch grows with the unit); the batch is the wide evaluator's.
+// The gates' sphere and plane counts come from DevScene::csg_counts. After the first pass over
+// the stream (the hit, `hin`, the parities) a radiance ray with an odd leaf takes a second over
+// its part t < 0 for the two container candidates. COUNT_ONLY: the first walk's gates alone.
+__device__ __forceinline__ void csg_skip_deep(GateSkips& sk, const DevScene& sc, int pc, int counts) {
+  sk.sph += sc.csg_counts[2 * pc]; sk.plane += sc.csg_counts[2 * pc + 1]; sk.other += (unsigned)counts >> 10;
+}
+__device__ __forceinline__ void csg_deep_save(const CsgDeepWords& st, int at, V3 o, V3 d) {
+  const double v[6] = {o.x, o.y, o.z, d.x, d.y, d.z};
+#pragma unroll
+  for (int e = 0; e < 6; ++e) {
+    st[at + 2 * e] = (uint32_t)__double2loint(v[e]);
+    st[at + 2 * e + 1] = (uint32_t)__double2hiint(v[e]);
+  }
+}
+__device__ __forceinline__ void csg_deep_load(const CsgDeepWords& st, int at, V3& o, V3& d) {
+  double v[6];
+#pragma unroll
+  for (int e = 0; e < 6; ++e) v[e] = __hiloint2double((int)st[at + 2 * e + 1], (int)st[at + 2 * e]);
+  o = v3(v[0], v[1], v[2]);
+  d = v3(v[3], v[4], v[5]);
+}
+template <bool SHADOW, bool COUNT_ONLY>
+__device__ __forceinline__ void csg_deep_eval(const DevScene& sc, const CsgUnit un, V3 o, V3 d, Hit& h, unsigned& disc,
+                                              GateSkips& sk) {
+  const unsigned lane = blockIdx.x * blockDim.x + threadIdx.x;
+  if (lane >= sc.csg_deep_lanes) return;  // (no launch is larger than its state buffer: rt_wavefront.hip, rt_render.cpp)
+  const CsgDeepWords st{sc.csg_deep_state + lane, (size_t)sc.csg_deep_lanes};
+  const int nw = sc.csg_deep_nw, lw = sc.csg_deep_lw, rays = 2 * nw + lw;
+  const int end = un.first + un.n;
+  const CsgRec* nodes = sc.csg_nodes + sc.csg_ops[un.first].arg;  // the unit's own node first
+  CsgDeepBatch b;
+  CsgDeepHit dh{h.t, h.key, h.hin};
+  CsgDeepTop2 top;
+  csg_deep_top2_init(top);
+  bool first = true;
+  // pass 0: the hit, `hin` and the parities; pass 1: the container candidates
+  for (int pass = 0; pass < (SHADOW || COUNT_ONLY ? 1 : 2); ++pass) {
+    if (pass == 1) {
+      uint32_t any = 0;
+      for (int i = 0; i < lw; ++i) any |= st[2 * nw + i];
+      if (!any) break;
+    }
+    for (int i = 0; i < (pass == 0 ? rays : 2 * nw); ++i) st[i] = 0u;
+    double wt = -INFINITY;  // below every root: (t, key) > (-inf, -1)
+    int32_t wk = -1;
+    for (;;) {
+      b.xs.n = 0;
+      bool more = false;
+      int lvl = 0, node = -1;
+      V3 co = o, cd = d;
+      for (int pc = un.first; pc < end;) {
+        const CsgOp op = sc.csg_ops[pc];
+        if (op.code == kCsgEnter) {
+          const CsgRec* c = sc.csg_nodes + op.arg;
+          const V3 lo = m34_point(c->m, co);
+          const V3 ld = v3(c->m[0] * cd.x + c->m[1] * cd.y + c->m[2] * cd.z, c->m[4] * cd.x + c->m[5] * cd.y + c->m[6] * cd.z,
+                           c->m[8] * cd.x + c->m[9] * cd.y + c->m[10] * cd.z);
+          if (lvl >= sc.csg_deep_levels || !bbox_intersects(c->lo, c->hi, lo, ld)) {  // csg.rs:116-118
+            if (first) csg_skip_deep(sk, sc, pc, op.counts);
+            pc = op.skip_to;
+            continue;
+          }
+          csg_deep_save(st, rays + 12 * lvl, co, cd);
+          ++lvl;
+          node = c->self;
+          co = lo; cd = ld;
+        } else if (op.code == kCsgExit) {
+          --lvl;
+          node = nodes[node].parent;
+          csg_deep_load(st, rays + 12 * lvl, co, cd);
+        } else if (op.code == kCsgGroup) {
+          if (!bbox_intersects((cGroupRec)sc.groups + op.arg, co, cd)) {  // group.rs:50-52, the ray it is handed
+            if (first) csg_skip_deep(sk, sc, pc, op.counts);
+            pc = op.skip_to;
+            continue;
+          }
+        } else if (COUNT_ONLY) {
+        } else if (op.code == kCsgTri) {
+          const TriRec* q = sc.csg_tris + op.arg;
+          double t;
+          if (csg_tri_roots(q, co, cd, t))
+            csg_batch_insert(b, kCsgListCap, t, (q->meta >> 1) << kKeyShift, (uint32_t)node | kCsgDeepTagTri, wt, wk, more);
+        } else {
+          const OtherRec* q = sc.csg_leaves + op.arg;
+          double t[4];
+          unsigned nd = 0;
+          const int n = csg_leaf_roots(q, co, cd, t, nd);
+          if (first) disc += nd;
+          const int k0 = (q->meta >> 1) << kKeyShift;
+          const uint32_t tag = (uint32_t)node | (uint32_t)q->gate << kCsgDeepTagSlotShift;
+          for (int i = 0; i < n; ++i) csg_batch_insert(b, kCsgListCap, t[i], k0 + i, tag, wt, wk, more);
+        }
+        ++pc;
+      }
+      first = false;
+      if (COUNT_ONLY) return;
+      bool done = false;
+      for (int i = 0; i < b.xs.n && !done; ++i) {
+        const double t = b.xs.t[i];
+        const int key = b.xs.key[i];
+        const uint32_t tag = b.tag[i];
+        if (pass == 0) {
+          const int r = csg_deep_step(nodes, st, nw, t, key, tag,
+                                      [&](int32_t k) { return !SHADOW || sc.shade[k >> kKeyShift].shadow != 0; }, dh);
+          if (r == kCsgDeepTriNeg) {
+            if (!SHADOW) push_container(h, t, key);
+          } else {
+            done = r == kCsgDeepDone;
+          }
+        } else if (t < 0.0) {
+          csg_deep_note(nodes, st, nw, t, key, tag, top);
+        } else {
+          done = true;
+        }
+      }
+      if (done || !more) break;
+      wt = b.xs.t[b.xs.n - 1];
+      wk = b.xs.key[b.xs.n - 1];
+    }
+  }
+  h.t = dh.t; h.key = dh.key; h.hin = dh.hin;
+  if (!SHADOW) {
+    if (top.k1 >= 0) push_container(h, top.t1, top.k1);
+    if (top.k2 >= 0) push_container(h, top.t2, top.k2);
+  }
+}
 // The units `units[0 .. n)`, each behind the gate of the groups around it (Group::intersect,
 // group.rs:49-58): the exhaustive paths pass the scene's full list in the reference's order,
 // the fast path the units outside the hierarchy (trace_rest; unit_trace walks the others).
-template <bool SHADOW, bool COUNT_ONLY>
+// DEEP = false: a kernel that is launched only for scenes without a deep unit (the batch kernels have such
+// twins: the deep evaluator stays out of them, and they keep their registers).
+template <bool SHADOW, bool COUNT_ONLY, bool DEEP = true>
 __device__ __forceinline__ void csg_units(const DevScene& sc, const CsgUnit* units, int n, V3 o, V3 d, Hit& h,
                                           unsigned& n_disc, GateSkips* skips) {
   GateSkips sk;
   unsigned disc = 0;
   for (int u = 0; u < n; ++u) {
     CsgUnit un = units[u];
+    const bool wide = (un.n & kCsgWide) != 0, deep = DEEP && (un.n & kCsgDeep) != 0;
     if (un.gate && !group_gate(sc, un.gate, o, d)) {
-      csg_skip(sk, un.counts);
+      if (deep) csg_skip_deep(sk, sc, un.first, un.counts);  // (its own Enter holds the unit's counts)
+      else csg_skip(sk, un.counts);
       continue;
     }
-    const bool wide = (un.n & kCsgWide) != 0;
-    un.n &= ~kCsgWide;
-    if (!COUNT_ONLY && wide) csg_wide_eval<SHADOW>(sc, un, o, d, h, disc, sk);
+    un.n &= ~kCsgKindMask;
+    if (deep) csg_deep_eval<SHADOW, COUNT_ONLY>(sc, un, o, d, h, disc, sk);
+    else if (!COUNT_ONLY && wide) csg_wide_eval<SHADOW>(sc, un, o, d, h, disc, sk);
     else csg_unit_eval<SHADOW, COUNT_ONLY>(sc, un, o, d, h, disc, sk);  // (a wide unit's gates alone: the same walk)
   }
   n_disc += disc;
@@ -770,7 +905,8 @@ __device__ __forceinline__ void alias_finish(const DevScene& sc, Hit& h) {
 // CSG: the Csg units too (csg_units): every unit, or on the fast path those outside the
 // units' hierarchy (fx_units; unit_trace walks the others).
 // ALIAS (with CSG): the alias classes too (alias_classes), every member on either path.
-template <bool SHADOW, bool QUADS = true, bool FAST = false, bool TRIS = QUADS, bool CSG = false, bool ALIAS = false>
+template <bool SHADOW, bool QUADS = true, bool FAST = false, bool TRIS = QUADS, bool CSG = false, bool ALIAS = false,
+          bool DEEP = true>
 __device__ __forceinline__ void trace_rest(const DevScene& sc, V3 o, V3 d, Hit& h, unsigned& n_disc,
                                            GateSkips* skips = nullptr) {
   cSphereGen sg = (cSphereGen)(FAST ? sc.fx_gen : sc.sph_gen);
@@ -821,8 +957,8 @@ __device__ __forceinline__ void trace_rest(const DevScene& sc, V3 o, V3 d, Hit& 
     }
   }
   if constexpr (CSG)
-    csg_units<SHADOW, false>(sc, FAST ? sc.fx_units : sc.csg_units, FAST ? sc.n_fx_units : sc.n_csg_units, o, d, h, n_disc,
-                             skips);
+    csg_units<SHADOW, false, DEEP>(sc, FAST ? sc.fx_units : sc.csg_units, FAST ? sc.n_fx_units : sc.n_csg_units, o, d, h,
+                                   n_disc, skips);
   if constexpr (ALIAS) alias_classes<SHADOW>(sc, o, d, h, n_disc, skips);
 }
 
@@ -890,13 +1026,14 @@ __device__ __forceinline__ void diag_test(cSphereDiag r, V3 o, V3 d, Hit& h, uns
 // the wavefront fallback when the trace image does not fit in LDS.
 // TRIS = false: a scene without solids or triangles (trace_rest). CSG: one with Csg units.
 // ALIAS (with CSG): one with alias classes.
-template <bool SHADOW, bool TRIS = true, bool CSG = false, bool ALIAS = false>
+// DEEP (with CSG): the deep units' evaluator too (csg_units).
+template <bool SHADOW, bool TRIS = true, bool CSG = false, bool ALIAS = false, bool DEEP = true>
 __device__ __forceinline__ void trace(const DevScene& sc, V3 o, V3 d, Hit& h, unsigned& n_disc,
                                       GateSkips* skips = nullptr) {
   hit_init(h);
   cSphereDiag sd = (cSphereDiag)sc.sph_diag;
   for (int j = 0; j < sc.n_diag; ++j) diag_test<SHADOW>(sd + j, o, d, h, n_disc);
-  trace_rest<SHADOW, true, false, TRIS, CSG, ALIAS>(sc, o, d, h, n_disc, skips);
+  trace_rest<SHADOW, true, false, TRIS, CSG, ALIAS, DEEP>(sc, o, d, h, n_disc, skips);
   hit_finish(h);
   if constexpr (ALIAS && !SHADOW) alias_finish(sc, h);
 }

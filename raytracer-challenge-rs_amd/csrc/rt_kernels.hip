@@ -20,7 +20,8 @@ namespace rtamd {
 // rt_hit_batch: 24 doubles per ray (layout in include/rt_render.h).
 // CSG: the scene has Csg units (kernels of their own: the others keep their registers).
 // ALIAS (with CSG): it has alias classes (again kernels of their own).
-template <bool CSG, bool ALIAS = false>
+// DEEP (with CSG): it has a deep Csg unit (again: the kernels of the other Csg scenes keep their registers).
+template <bool CSG, bool ALIAS = false, bool DEEP = false>
 __device__ __forceinline__ void hit_body(const DevScene& sc, const double* rays, int n, double* out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -28,7 +29,7 @@ __device__ __forceinline__ void hit_body(const DevScene& sc, const double* rays,
   const V3 d = v3(rays[6 * i + 3], rays[6 * i + 4], rays[6 * i + 5]);
   Hit h;
   unsigned nd = 0;
-  trace<false, true, CSG, ALIAS>(sc, o, d, h, nd);
+  trace<false, true, CSG, ALIAS, DEEP>(sc, o, d, h, nd);
   double* r = out + (size_t)i * 24;
   for (int k = 0; k < 24; ++k) r[k] = 0.0;
   r[0] = -1.0;
@@ -55,9 +56,15 @@ __global__ __launch_bounds__(256) void hit_kernel_csg(DevScene sc, const double*
 __global__ __launch_bounds__(256) void hit_kernel_alias(DevScene sc, const double* rays, int n, double* out) {
   hit_body<true, true>(sc, rays, n, out);
 }
+__global__ __launch_bounds__(256) void hit_kernel_deep(DevScene sc, const double* rays, int n, double* out) {
+  hit_body<true, false, true>(sc, rays, n, out);
+}
+__global__ __launch_bounds__(256) void hit_kernel_alias_deep(DevScene sc, const double* rays, int n, double* out) {
+  hit_body<true, true, true>(sc, rays, n, out);
+}
 
 // rt_is_shadowed_batch: World::is_shadowed for each point against one light.
-template <bool CSG, bool ALIAS = false>
+template <bool CSG, bool ALIAS = false, bool DEEP = false>
 __device__ __forceinline__ void shadow_body(const DevScene& sc, const double* pts, int n, int light, uint8_t* out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -68,7 +75,7 @@ __device__ __forceinline__ void shadow_body(const DevScene& sc, const double* pt
   const V3 d = vnormalize(v);
   Hit h;
   unsigned nd = 0;
-  trace<true, true, CSG, ALIAS>(sc, p, d, h, nd);
+  trace<true, true, CSG, ALIAS, DEEP>(sc, p, d, h, nd);
   out[i] = (h.key >= 0 && h.t < distance) ? 1 : 0;
 }
 __global__ __launch_bounds__(256) void shadow_kernel(DevScene sc, const double* pts, int n, int light,
@@ -83,9 +90,21 @@ __global__ __launch_bounds__(256) void shadow_kernel_alias(DevScene sc, const do
                                                            uint8_t* out) {
   shadow_body<true, true>(sc, pts, n, light, out);
 }
+__global__ __launch_bounds__(256) void shadow_kernel_deep(DevScene sc, const double* pts, int n, int light,
+                                                          uint8_t* out) {
+  shadow_body<true, false, true>(sc, pts, n, light, out);
+}
+__global__ __launch_bounds__(256) void shadow_kernel_alias_deep(DevScene sc, const double* pts, int n, int light,
+                                                                uint8_t* out) {
+  shadow_body<true, true, true>(sc, pts, n, light, out);
+}
 
 hipError_t launch_hit(const DevScene& sc, const double* d_rays, int n, double* d_out, hipStream_t s) {
-  if (sc.n_alias_rec > 0) hipLaunchKernelGGL(hit_kernel_alias, dim3((n + 255) / 256), dim3(256), 0, s, sc, d_rays, n, d_out);
+  const bool deep = sc.csg_deep_levels > 0;  // (a scene with a deep unit: the kernels that hold its evaluator)
+  if (deep && sc.n_alias_rec > 0)
+    hipLaunchKernelGGL(hit_kernel_alias_deep, dim3((n + 255) / 256), dim3(256), 0, s, sc, d_rays, n, d_out);
+  else if (deep) hipLaunchKernelGGL(hit_kernel_deep, dim3((n + 255) / 256), dim3(256), 0, s, sc, d_rays, n, d_out);
+  else if (sc.n_alias_rec > 0) hipLaunchKernelGGL(hit_kernel_alias, dim3((n + 255) / 256), dim3(256), 0, s, sc, d_rays, n, d_out);
   else if (sc.n_csg_units > 0) hipLaunchKernelGGL(hit_kernel_csg, dim3((n + 255) / 256), dim3(256), 0, s, sc, d_rays, n, d_out);
   else hipLaunchKernelGGL(hit_kernel, dim3((n + 255) / 256), dim3(256), 0, s, sc, d_rays, n, d_out);
   return hipGetLastError();
@@ -93,7 +112,12 @@ hipError_t launch_hit(const DevScene& sc, const double* d_rays, int n, double* d
 
 hipError_t launch_shadow(const DevScene& sc, const double* d_pts, int n, int light, uint8_t* d_out,
                          hipStream_t s) {
-  if (sc.n_alias_rec > 0)
+  const bool deep = sc.csg_deep_levels > 0;
+  if (deep && sc.n_alias_rec > 0)
+    hipLaunchKernelGGL(shadow_kernel_alias_deep, dim3((n + 255) / 256), dim3(256), 0, s, sc, d_pts, n, light, d_out);
+  else if (deep)
+    hipLaunchKernelGGL(shadow_kernel_deep, dim3((n + 255) / 256), dim3(256), 0, s, sc, d_pts, n, light, d_out);
+  else if (sc.n_alias_rec > 0)
     hipLaunchKernelGGL(shadow_kernel_alias, dim3((n + 255) / 256), dim3(256), 0, s, sc, d_pts, n, light, d_out);
   else if (sc.n_csg_units > 0)
     hipLaunchKernelGGL(shadow_kernel_csg, dim3((n + 255) / 256), dim3(256), 0, s, sc, d_pts, n, light, d_out);

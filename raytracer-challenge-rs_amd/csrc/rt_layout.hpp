@@ -134,9 +134,28 @@ static_assert(sizeof(CsgRec) == 192, "CsgRec must stay 192 B");
 // development knob csg_wide_all): the streamed evaluator (csg_wide_eval), never the
 // units' hierarchy.
 constexpr int32_t kCsgWide = 1 << 30;
+// `n` | kCsgDeep: a DEEP unit (rt_scene_create_ex with RT_SCENE_DEEP_CSG: one beyond a cap of the
+// other two kinds, or every unit under the development knob csg_deep_all): csg_deep_eval, whose
+// per-lane state scales with the unit and lives in the launch's own buffer (DevScene::
+// csg_deep_state), never the units' hierarchy. Its gates read their sphere and plane counts from
+// DevScene::csg_counts (two words per op of the program: the packed fields hold 31 of each, and
+// are zero in a deep unit's ops and unit record); a leaf of kinds 0-4 has its number among the
+// unit's such leaves in OtherRec::gate, as a wide unit's.
+constexpr int32_t kCsgDeep = 1 << 29;
+constexpr int32_t kCsgKindMask = kCsgWide | kCsgDeep;
+// What a deep unit's batch tag holds (rt_csg.hpp kCsgDeepTag*): include/rt_render.h's
+// RT_CSG_DEEP_MAX_NODES Csg nodes and RT_CSG_DEEP_MAX_LEAVES leaves of kinds 0-4 in one unit.
+constexpr int32_t kCsgDeepMaxNodes = 1 << 15, kCsgDeepMaxLeaves = 1 << 16;
 struct alignas(16) CsgUnit {
   int32_t first, n, gate, counts;
 };
+// The deep state of one lane, in 32-bit words (word i of lane l at i * lanes + l, so a wave's
+// accesses coalesce): the filter bits inl and inr, one bit each per Csg node of the unit (nw words
+// each), the parity bits of the leaves of kinds 0-4 (lw words), and per open level of the ray
+// chain the ray its Enter found (12 words: origin and direction).
+constexpr int32_t csg_deep_words(int32_t nodes, int32_t leaves, int32_t levels) {
+  return 2 * ((nodes + 31) / 32) + (leaves + 31) / 32 + 12 * levels;
+}
 static_assert(sizeof(QuadRec) == 128, "QuadRec must stay 128 B");
 // ---- Alias classes (rt_scene_create_aliased): shapes the caller's structural `==` holds
 // between, every two of a class (exact and near duplicates). In the `containers` walk of
@@ -424,6 +443,16 @@ struct DevScene {
   const int32_t* alias_of;
   int32_t n_alias_rec, n_alias_cls;
   int32_t n_alias_sph, n_alias_planes, n_alias_other, pad_alias;
+  // Deep Csg units (rt_scene_create_ex, RT_SCENE_DEEP_CSG; csg_deep_eval). `csg_counts`: per op of
+  // the programs its spheres and planes below (two words; nullptr without a deep unit).
+  // csg_deep_nw / _lw / _levels: the scene's largest deep unit in filter words, parity words and
+  // levels (all 0: no deep unit). csg_deep_state / _lanes: the launch's own state buffer and the
+  // lanes it holds (the workspace's or the batch call's: set in its copy of this struct, never in
+  // the scene's), csg_deep_words(...) * lanes words.
+  const uint32_t* csg_counts;
+  uint32_t* csg_deep_state;
+  uint32_t csg_deep_lanes;
+  int32_t csg_deep_nw, csg_deep_lw, csg_deep_levels;
 };
 
 constexpr int32_t kOwnOutside = 0x40000000, kOwnIndex = 0x3FFFFFFF;  // DevScene::obj_diag

@@ -809,7 +809,9 @@ int rt_is_shadowed_batch(const rt_scene* scene, const double* points, size_t n, 
   rc = ensure_dev_buffer(&c->d_out, &c->out_cap, (n + 7) / 8);
   if (rc != RT_OK) return rc;
   RT_HIP(hipMemcpyAsync(c->d_in, points, n * 3 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  RT_HIP(launch_shadow(s->dev, c->d_in, (int)n, (int)light, (uint8_t*)c->d_out, c->stream));
+  DevScene sc;
+  if ((rc = batch_scene(s, c, n, &sc)) != RT_OK) return rc;
+  RT_HIP(launch_shadow(sc, c->d_in, (int)n, (int)light, (uint8_t*)c->d_out, c->stream));
   RT_HIP(hipMemcpyAsync(out, c->d_out, n, hipMemcpyDeviceToHost, c->stream));
   RT_HIP(hipStreamSynchronize(c->stream));
   return RT_OK;
@@ -833,7 +835,9 @@ int rt_hit_batch(const rt_scene* scene, const double* rays, size_t n, double* ou
   rc = ensure_dev_buffer(&c->d_out, &c->out_cap, n * 24);
   if (rc != RT_OK) return rc;
   RT_HIP(hipMemcpyAsync(c->d_in, rays, n * 6 * sizeof(double), hipMemcpyHostToDevice, c->stream));
-  RT_HIP(launch_hit(s->dev, c->d_in, (int)n, c->d_out, c->stream));
+  DevScene sc;
+  if ((rc = batch_scene(s, c, n, &sc)) != RT_OK) return rc;
+  RT_HIP(launch_hit(sc, c->d_in, (int)n, c->d_out, c->stream));
   RT_HIP(hipMemcpyAsync(out24, c->d_out, n * 24 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   RT_HIP(hipStreamSynchronize(c->stream));
   return RT_OK;

@@ -13,6 +13,8 @@ using namespace rtapi;
 
 static_assert(kCsgMaxLeaves == RT_CSG_MAX_LEAVES && kCsgMaxDepth == RT_CSG_MAX_DEPTH && kCsgMaxNodes == RT_CSG_MAX_NODES,
               "the Csg caps of include/rt_render.h are rt_csg.hpp's");
+static_assert(kCsgDeepMaxNodes == RT_CSG_DEEP_MAX_NODES && kCsgDeepMaxLeaves == RT_CSG_DEEP_MAX_LEAVES,
+              "the deep units' format limits of include/rt_render.h are rt_layout.hpp's");
 
 namespace {
 
@@ -38,7 +40,7 @@ int find_duplicate(const rt_shape_desc* s, size_t n, const std::vector<const rt_
 int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* shape_node, const int32_t* shape_side,
                 const rt_node_desc* nodes, size_t n_nodes, const rt_triangle_desc* tri_descs, size_t n_tris,
                 const rt_light_desc* lights, size_t n_lights, bool aliased, const int32_t* equal_pairs, size_t n_pairs,
-                int device, rt_scene** out) {
+                bool deep_csg, int device, rt_scene** out) {
   if (!out || (n_shapes && !shapes) || (n_lights && !lights) || (n_nodes && (!nodes || !shape_node)) ||
       (n_tris && !tri_descs))
     return fail(RT_ERR_INVALID_ARGUMENT, "null pointer");
@@ -50,7 +52,9 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
       return fail(RT_ERR_INVALID_ARGUMENT, "node " + std::to_string(g) + ": its parent must be -1 or an earlier node");
   // ---- Csg nodes: each node's unit (the outermost Csg at or above it, -1: none) and the
   // Csg nodes from that unit down to it
-  std::vector<int32_t> unit_of_node(n_nodes, -1), csg_level(n_nodes, 0);
+  // (deep_csg, rt_scene_create_ex: no cap; a unit beyond one is DEEP, rt_layout.hpp kCsgDeep)
+  std::vector<int32_t> unit_of_node(n_nodes, -1), csg_level(n_nodes, 0), unit_levels(n_nodes, 0);
+  std::vector<char> deep_unit(n_nodes, 0);
   bool any_csg = false;
   for (size_t g = 0; g < n_nodes; ++g) {
     const rt_node_desc& nd = nodes[g];
@@ -65,7 +69,16 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
     unit_of_node[g] = up >= 0 ? up : (csg ? (int32_t)g : -1);
     csg_level[g] = (up >= 0 ? csg_level[(size_t)nd.parent] : 0) + (csg ? 1 : 0);
     any_csg = any_csg || csg;
-    if (csg_level[g] > kCsgMaxDepth)
+    if (unit_of_node[g] >= 0) {
+      int32_t& lv = unit_levels[(size_t)unit_of_node[g]];
+      lv = std::max(lv, csg_level[g]);
+    }
+    if (csg_level[g] > kCsgMaxDepth && deep_csg) {
+      deep_unit[(size_t)unit_of_node[g]] = 1;
+      if (csg_level[g] > RT_CSG_DEEP_MAX_LEVELS)
+        return fail(RT_ERR_UNSUPPORTED_SHAPE, "node " + std::to_string(g) + ": more than RT_CSG_DEEP_MAX_LEVELS = " +
+                                                  std::to_string(RT_CSG_DEEP_MAX_LEVELS) + " nested Csg nodes");
+    } else if (csg_level[g] > kCsgMaxDepth)
       return fail(RT_ERR_UNSUPPORTED_SHAPE, "node " + std::to_string(g) + ": more than RT_CSG_MAX_DEPTH = " +
                                                 std::to_string(kCsgMaxDepth) + " nested Csg nodes");
   }
@@ -113,14 +126,25 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
         wide_unit[(size_t)u] = 1;
         continue;
       }
-      if (++n_leaves[(size_t)u] > kCsgMaxLeaves)
+      if (++n_leaves[(size_t)u] > kCsgMaxLeaves && deep_csg) {
+        deep_unit[(size_t)u] = 1;
+        if (n_leaves[(size_t)u] > kCsgDeepMaxLeaves)
+          return fail(RT_ERR_UNSUPPORTED_SHAPE, "node " + std::to_string(u) + ": more than RT_CSG_DEEP_MAX_LEAVES = " +
+                                                    std::to_string(kCsgDeepMaxLeaves) +
+                                                    " primitives under one Csg (the deep units' batch tag)");
+      } else if (n_leaves[(size_t)u] > kCsgMaxLeaves)
         return fail(RT_ERR_UNSUPPORTED_SHAPE, "node " + std::to_string(u) + ": more than RT_CSG_MAX_LEAVES = " +
                                                   std::to_string(kCsgMaxLeaves) +
                                                   " primitives under one Csg (Sphere, Plane, Cube, Cylinder, Cone; triangles are not counted)");
     }
     for (size_t g = 0; g < n_nodes; ++g) {
       const int32_t u = unit_of_node[g];
-      if (u >= 0 && nodes[g].kind == RT_NODE_CSG && ++n_csg_nodes[(size_t)u] > kCsgMaxNodes && wide_unit[(size_t)u])
+      if (u < 0 || nodes[g].kind != RT_NODE_CSG) continue;
+      if (++n_csg_nodes[(size_t)u] > kCsgDeepMaxNodes)  // (only with deep_csg: 16 leaves or 4 levels hold fewer)
+        return fail(RT_ERR_UNSUPPORTED_SHAPE, "node " + std::to_string(u) + ": more than RT_CSG_DEEP_MAX_NODES = " +
+                                                  std::to_string(kCsgDeepMaxNodes) + " Csg nodes in one Csg (the deep units' batch tag)");
+      if (n_csg_nodes[(size_t)u] > kCsgMaxNodes && wide_unit[(size_t)u] && deep_csg) deep_unit[(size_t)u] = 1;
+      else if (n_csg_nodes[(size_t)u] > kCsgMaxNodes && wide_unit[(size_t)u])
         return fail(RT_ERR_UNSUPPORTED_SHAPE, "node " + std::to_string(u) + ": more than RT_CSG_MAX_NODES = " +
                                                   std::to_string(kCsgMaxNodes) + " Csg nodes in one Csg with triangles below it");
     }
@@ -357,6 +381,8 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
   std::vector<CsgUnit> csg_units;
   std::vector<CsgOp> csg_ops;
   std::vector<CsgRec> csg_nodes;
+  std::vector<uint32_t> csg_counts;  // per op: spheres, planes below (what a deep unit's gates read)
+  long long deep_plan[4] = {0, 0, 0, 0};  // deep units; the largest one's levels, nodes, leaves of kinds 0-4
   if (any_csg) {
     // a node's children: sub-nodes and shapes, by the first shape below them (the shapes come depth first)
     struct Child { int32_t first, side, node, shape; };
@@ -372,7 +398,7 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
         kids[(size_t)nodes[g].parent].push_back(Child{first_shape[g], nodes[g].side, (int32_t)g, -1});
     for (auto& k : kids) std::stable_sort(k.begin(), k.end(), [](const Child& a, const Child& b) { return a.first < b.first; });
     int32_t next_shape = 0, unit_rec = 0, next_slot = 0;
-    bool in_order = true, two_sided = true;
+    bool in_order = true, two_sided = true, deep_now = false;
     // emits the node's subtree; cnt: its leaves by counter class; above: the CsgRec of the
     // innermost Csg above the node (-1: none, the node is the unit's own)
     std::function<void(int32_t, int32_t*, int32_t)> emit = [&](int32_t g, int32_t* cnt, int32_t above) {
@@ -421,7 +447,12 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
         csg_ops.push_back(CsgOp{kCsgExit, rec, 0, 0});
       }
       csg_ops[at].skip_to = (int32_t)csg_ops.size();
-      csg_ops[at].counts = csg_pack_counts(mine);
+      // (a deep unit's spheres and planes are in csg_counts alone: the packed fields hold 31 each)
+      const int32_t others[3] = {0, 0, mine[2]};
+      csg_ops[at].counts = csg_pack_counts(deep_now ? others : mine);
+      csg_counts.resize(2 * csg_ops.size(), 0u);
+      csg_counts[2 * at] = (uint32_t)mine[0];
+      csg_counts[2 * at + 1] = (uint32_t)mine[1];
       for (int c = 0; c < 3; ++c) cnt[c] += mine[c];
     };
     for (size_t g = 0; g < n_nodes; ++g) {
@@ -433,10 +464,19 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
       next_shape = first_shape[g] == INT32_MAX ? 0 : first_shape[g];
       unit_rec = (int32_t)csg_nodes.size();
       next_slot = 0;
+      deep_now = deep_unit[g] || g_csg_deep_all;
       emit((int32_t)g, cnt, -1);
       u.n = (int32_t)csg_ops.size() - u.first;
-      if (wide_unit[g] || g_csg_wide_all) u.n |= kCsgWide;
-      u.counts = csg_pack_counts(cnt);
+      if (deep_now) u.n |= kCsgDeep;
+      else if (wide_unit[g] || g_csg_wide_all) u.n |= kCsgWide;
+      const int32_t others[3] = {0, 0, cnt[2]};
+      u.counts = csg_pack_counts(deep_now ? others : cnt);
+      if (deep_now) {
+        ++deep_plan[0];
+        deep_plan[1] = std::max<long long>(deep_plan[1], unit_levels[g]);
+        deep_plan[2] = std::max<long long>(deep_plan[2], (long long)csg_nodes.size() - unit_rec);
+        deep_plan[3] = std::max<long long>(deep_plan[3], next_slot);
+      }
       csg_units.push_back(u);
     }
     if (!two_sided) return fail(RT_ERR_INVALID_ARGUMENT, "a Csg node needs exactly one left and one right child");
@@ -493,8 +533,8 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
   std::vector<CsgUnit> urec, fx_units;
   std::vector<double> unit_boxes;
   for (const CsgUnit& u : csg_units) {
-    // (a wide unit has no box: it stays in the loop, behind the reference's own Csg gate)
-    if (!(u.n & kCsgWide) && csg_unit_box(csg_ops.data(), u.first, u.n, csg_nodes.data(), csg_leaves.data(), blo, bhi)) {
+    // (a wide or deep unit has no box: it stays in the loop, behind the reference's own Csg gate)
+    if (!(u.n & kCsgKindMask) && csg_unit_box(csg_ops.data(), u.first, u.n, csg_nodes.data(), csg_leaves.data(), blo, bhi)) {
       urec.push_back(u);
       unit_boxes.insert(unit_boxes.end(), blo, blo + 3);
       unit_boxes.insert(unit_boxes.end(), bhi, bhi + 3);
@@ -591,7 +631,9 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
   const size_t o_ac = align(o_ar + (alias_rec.size() + 1) * sizeof(OtherRec));
   const size_t o_ao = align(o_ac + (alias_tab.size() + 1) * sizeof(AliasClass));
   const size_t o_ct = align(o_ao + (alias_of.size() + 1) * sizeof(int32_t));
-  const size_t total = align(o_ct + (csg_tris.size() + 1) * sizeof(TriRec)) + 256;
+  if (!deep_plan[0]) csg_counts.clear();  // (only a deep unit's gates read them)
+  const size_t o_dc = align(o_ct + (csg_tris.size() + 1) * sizeof(TriRec));
+  const size_t total = align(o_dc + (csg_counts.size() + 1) * sizeof(uint32_t)) + 256;
   std::vector<unsigned char> host(total, 0);
   if (!diag.empty()) std::memcpy(&host[o_diag], diag.data(), diag.size() * sizeof(SphereDiag));
   if (!gen.empty()) std::memcpy(&host[o_gen], gen.data(), gen.size() * sizeof(SphereGen));
@@ -645,6 +687,7 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
   if (!csg_nodes.empty()) std::memcpy(&host[o_cn], csg_nodes.data(), csg_nodes.size() * sizeof(CsgRec));
   if (!csg_leaves.empty()) std::memcpy(&host[o_cl], csg_leaves.data(), csg_leaves.size() * sizeof(OtherRec));
   if (!csg_tris.empty()) std::memcpy(&host[o_ct], csg_tris.data(), csg_tris.size() * sizeof(TriRec));
+  if (!csg_counts.empty()) std::memcpy(&host[o_dc], csg_counts.data(), csg_counts.size() * sizeof(uint32_t));
   if (!ubvh.empty()) std::memcpy(&host[o_ub], ubvh.data(), ubvh.size() * sizeof(BvhNode));
   if (!urec.empty()) std::memcpy(&host[o_ur], urec.data(), urec.size() * sizeof(CsgUnit));
   if (!fx_units.empty()) std::memcpy(&host[o_ux], fx_units.data(), fx_units.size() * sizeof(CsgUnit));
@@ -741,6 +784,13 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
   s->dev.csg_nodes = (const CsgRec*)(b + o_cn);
   s->dev.csg_leaves = (const OtherRec*)(b + o_cl);
   s->dev.csg_tris = (const TriRec*)(b + o_ct);
+  s->dev.csg_counts = csg_counts.empty() ? nullptr : (const uint32_t*)(b + o_dc);
+  if (deep_plan[0]) {  // (the state buffer itself is each launch's own: Wavefront, rt_scene::HostCtx)
+    s->dev.csg_deep_levels = (int32_t)deep_plan[1];
+    s->dev.csg_deep_nw = (int32_t)((deep_plan[2] + 31) / 32);
+    s->dev.csg_deep_lw = (int32_t)((deep_plan[3] + 31) / 32);
+  }
+  for (int k = 0; k < 4; ++k) s->csg_deep_plan[k] = deep_plan[k];
   s->dev.n_csg_units = (int32_t)csg_units.size();
   s->dev.n_csg_sph = n_csg_kind[0];
   s->dev.n_csg_planes = n_csg_kind[1];
@@ -823,7 +873,7 @@ int rt_scene_create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int
                          int device, rt_scene** out) {
   return guarded([&]() -> int {
     return create_tree(shapes, n_shapes, shape_node, shape_side, nodes, n_nodes, tri_descs, n_tris, lights, n_lights,
-                       false, nullptr, 0, device, out);
+                       false, nullptr, 0, false, device, out);
   });
 }
 
@@ -834,7 +884,23 @@ int rt_scene_create_aliased(const rt_shape_desc* shapes, size_t n_shapes, const 
   return guarded([&]() -> int {
     if (n_pairs && !equal_pairs) return fail(RT_ERR_INVALID_ARGUMENT, "null pointer");
     return create_tree(shapes, n_shapes, shape_node, shape_side, nodes, n_nodes, tri_descs, n_tris, lights, n_lights,
-                       true, equal_pairs, n_pairs, device, out);
+                       true, equal_pairs, n_pairs, false, device, out);
+  });
+}
+
+int rt_scene_create_ex(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* shape_node, const int32_t* shape_side,
+                       const rt_node_desc* nodes, size_t n_nodes, const rt_triangle_desc* tri_descs, size_t n_tris,
+                       const rt_light_desc* lights, size_t n_lights, const int32_t* equal_pairs, size_t n_pairs,
+                       uint32_t flags, int device, rt_scene** out) {
+  return guarded([&]() -> int {
+    if (flags & ~(uint32_t)(RT_SCENE_ALIASED | RT_SCENE_DEEP_CSG))
+      return fail(RT_ERR_INVALID_ARGUMENT, "unknown flag (RT_SCENE_ALIASED, RT_SCENE_DEEP_CSG)");
+    const bool aliased = (flags & RT_SCENE_ALIASED) != 0;
+    if (!aliased && (equal_pairs || n_pairs))
+      return fail(RT_ERR_INVALID_ARGUMENT, "equal pairs without RT_SCENE_ALIASED");
+    if (n_pairs && !equal_pairs) return fail(RT_ERR_INVALID_ARGUMENT, "null pointer");
+    return create_tree(shapes, n_shapes, shape_node, shape_side, nodes, n_nodes, tri_descs, n_tris, lights, n_lights,
+                       aliased, equal_pairs, n_pairs, (flags & RT_SCENE_DEEP_CSG) != 0, device, out);
   });
 }
 

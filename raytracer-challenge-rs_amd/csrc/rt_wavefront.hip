@@ -70,6 +70,7 @@ Wavefront::~Wavefront() {
   if (d_gsh_) (void)hipFree(d_gsh_);
   if (d_cnt_) (void)hipFree(d_cnt_);
   if (d_shard_) (void)hipFree(d_shard_);
+  if (d_deep_) (void)hipFree(d_deep_);
   if (d_prim_) (void)hipFree(d_prim_);
   if (d_frames_) (void)hipFree(d_frames_);
   if (h_rec_) (void)hipHostFree(h_rec_);
@@ -416,9 +417,45 @@ WfArgs Wavefront::job_args(const WfJob& job, unsigned n0, unsigned frame_real) c
   return a;
 }
 
-hipError_t Wavefront::render(const DevScene& sc, const WfJob& job, hipStream_t stream, WfSizing& sz,
+DevScene Wavefront::deep_side_scene(const DevScene& sc) const {
+  DevScene side = sc;
+  if (sc.csg_deep_state) side.csg_deep_state = sc.csg_deep_state + deep_set_;
+  return side;
+}
+
+hipError_t Wavefront::with_deep_state(int sets, DevScene* out) {
+  const DevScene& sc = *out;
+  deep_asked_ = 0;
+  if (sc.csg_deep_levels <= 0) return hipSuccess;  // no deep unit: no buffer
+  if (deep_lanes_ == 0) {
+    int dev = 0, n_cu = 0, per_cu = 0;
+    WF_CHECK(hipGetDevice(&dev));
+    WF_CHECK(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+    WF_CHECK(hipDeviceGetAttribute(&per_cu, hipDeviceAttributeMaxThreadsPerMultiProcessor, dev));
+    deep_lanes_ = (unsigned)std::max(n_cu, 1) * (unsigned)std::max(per_cu, kTraceBlock);
+  }
+  deep_set_ = (size_t)csg_deep_words(32 * sc.csg_deep_nw, 32 * sc.csg_deep_lw, sc.csg_deep_levels) * deep_lanes_;
+  const size_t need = deep_set_ * (size_t)sets;
+  if (deep_cap_ < need) {
+    if (d_deep_) (void)hipFree(d_deep_);
+    d_deep_ = nullptr;
+    deep_cap_ = 0;
+    if (hipMalloc((void**)&d_deep_, need * sizeof(uint32_t)) != hipSuccess) {
+      (void)hipGetLastError();
+      deep_asked_ = need * sizeof(uint32_t);
+      return hipErrorOutOfMemory;
+    }
+    deep_cap_ = need;
+  }
+  out->csg_deep_state = d_deep_;
+  out->csg_deep_lanes = deep_lanes_;
+  return hipSuccess;
+}
+
+hipError_t Wavefront::render(const DevScene& scene, const WfJob& job, hipStream_t stream, WfSizing& sz,
                              const WfTuning& tn, bool solo) {
   if (!wf_job_valid(job)) return hipErrorInvalidValue;
+  DevScene sc = scene;
   const DevCamera& cam = job.cam;
   const bool camera_mode = job.camera_mode();
   const unsigned max_depth = job.max_depth, n_frames = job.n_frames, flags = job.flags;
@@ -432,6 +469,7 @@ hipError_t Wavefront::render(const DevScene& sc, const WfJob& job, hipStream_t s
   const bool bvh = tn.accel != 0 && !exhaustive && (sc.n_bvh > 0 || sc.n_obvh > 0 || sc.n_lbvh > 0 || sc.n_tbvh > 0 ||
                                                       sc.n_ubvh > 0);
   const bool fused = bvh;
+  WF_CHECK(with_deep_state(fused ? 1 : 2, &sc));
   // (a counted render of a scene with groups traces every shadow ray: the reference's shape
   // tests then come from the group gates each ray met, GateSkips)
   const bool skip_shadow = !exhaustive && tn.skip_shadow != 0 && !(count && sc.n_groups > 0);
@@ -746,8 +784,10 @@ hipError_t Wavefront::render_exhaustive(const DevScene& sc, const WfJob& job, hi
         forked = true;
       }
       WF_CHECK(pmark(sh_stream, WF_SHADOW, true));
-      if (sc.n_alias_rec > 0) WF_CHECK((launch_shadow_exh<true, true, true>(sc, a, gen_lds, sh_stream, tn)));
-      else if (sc.n_csg_units > 0) WF_CHECK((launch_shadow_exh<true, true>(sc, a, gen_lds, sh_stream, tn)));
+      // (beside the next generation's closest-hit launch on the side stream: the deep Csg units' second state set)
+      const DevScene sc_sh = sh_stream != stream ? deep_side_scene(sc) : sc;
+      if (sc.n_alias_rec > 0) WF_CHECK((launch_shadow_exh<true, true, true>(sc_sh, a, gen_lds, sh_stream, tn)));
+      else if (sc.n_csg_units > 0) WF_CHECK((launch_shadow_exh<true, true>(sc_sh, a, gen_lds, sh_stream, tn)));
       else if (sc.n_quads > 0 || sc.n_tris > 0) WF_CHECK(launch_shadow_exh<true>(sc, a, gen_lds, sh_stream, tn));
       else WF_CHECK(launch_shadow_exh<false>(sc, a, gen_lds, sh_stream, tn));
       WF_CHECK(pmark(sh_stream, WF_SHADOW, false));

@@ -455,8 +455,23 @@ class Wavefront {
   // generation's (lane -1: the render had no such launch, or was not fused).
   const WfImagePlan& plan_primary() const { return plan_primary_; }
   const WfImagePlan& plan_secondary() const { return plan_secondary_; }
+  // The bytes of deep-Csg state the last render asked for and could not allocate (it returned
+  // hipErrorOutOfMemory), else 0.
+  size_t deep_asked() const { return deep_asked_; }
 
  private:
+  // The scene as this workspace's launches see it: with this workspace's state buffer for the
+  // deep Csg units (DevScene::csg_deep_state), one lane for every thread the device holds at
+  // once (no launch's grid is larger: occupancy_grid). The buffer belongs to the workspace, not
+  // to the scene: renders of one scene on several streams run at once. `sets`: 2 for the
+  // exhaustive pipeline, whose shadow traces run on the side stream beside the next generation's
+  // closest-hit launch (deep_side_scene: the second set is theirs), else 1.
+  hipError_t with_deep_state(int sets, DevScene* sc);
+  DevScene deep_side_scene(const DevScene& sc) const;
+  uint32_t* d_deep_ = nullptr;
+  size_t deep_cap_ = 0, deep_asked_ = 0;  // words; bytes
+  size_t deep_set_ = 0;                   // words of one set
+  unsigned deep_lanes_ = 0;
   // n0: the pass's generation-0 slots (a batch: n_frames x the padded frame), frame_real: one frame's root rays
   hipError_t render_fast(const DevScene& sc, const WfJob& job, unsigned n0, unsigned frame_real, hipStream_t stream,
                          WfSizing& sz, bool skip_shadow, const WfTuning& tn);

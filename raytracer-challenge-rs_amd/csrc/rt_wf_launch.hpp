@@ -25,6 +25,15 @@ static int occupancy_grid(K kern, int block, size_t lds, unsigned n) {
   return (int)std::max(g, 1LL);
 }
 
+// The deep Csg units' state buffer of the scene a launch passes (its first argument, where that is a
+// DevScene) holds a lane for every thread of the grid: csg_deep_eval indexes it by the thread's number.
+template <typename A, typename... Rest>
+inline bool deep_state_holds(unsigned, unsigned, const A&, const Rest&...) { return true; }
+template <typename... Rest>
+inline bool deep_state_holds(unsigned grid, unsigned block, const DevScene& sc, const Rest&...) {
+  return sc.csg_deep_levels <= 0 || (unsigned long long)grid * block <= sc.csg_deep_lanes;
+}
+
 // One launch over n items with `dyn` bytes of dynamic LDS: the kernel's limit
 // raised to it, the occupancy grid, and the launch, carrying the profiling
 // events e0 / e1 in the dispatch itself when given (no event packets between
@@ -34,6 +43,8 @@ static hipError_t wf_launch(K kern, int block, size_t dyn, unsigned n, hipStream
                             const Args&... args) {
   if (dyn > 0) WF_CHECK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn));
   const dim3 grid(occupancy_grid(kern, block, dyn, n));
+  // (a launch larger than the workspace's deep state is refused here, not answered wrongly on the device)
+  if (!deep_state_holds(grid.x, (unsigned)block, args...)) return hipErrorInvalidValue;
   if (e0) hipExtLaunchKernelGGL(kern, grid, dim3(block), dyn, stream, e0, e1, 0, args...);
   else hipLaunchKernelGGL(kern, grid, dim3(block), dyn, stream, args...);
   return hipGetLastError();

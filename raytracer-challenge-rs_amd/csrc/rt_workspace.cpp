@@ -17,6 +17,27 @@ int ensure_dev_buffer(double** buf, size_t* cap, size_t need) {
   return RT_OK;
 }
 
+int batch_scene(const rt_scene* s, rt_scene::HostCtx* c, size_t n, DevScene* out) {
+  *out = s->dev;
+  const size_t words = (size_t)csg_deep_words(32 * s->dev.csg_deep_nw, 32 * s->dev.csg_deep_lw, s->dev.csg_deep_levels);
+  if (!s->csg_deep_plan[0] || n == 0) return RT_OK;
+  const size_t lanes = (n + 255) / 256 * 256, need = words * lanes;  // (the batch kernels' grid: blocks of 256)
+  if (c->deep_cap < need) {
+    if (c->d_deep) (void)hipFree(c->d_deep);
+    c->d_deep = nullptr;
+    c->deep_cap = 0;
+    if (hipMalloc((void**)&c->d_deep, need * sizeof(uint32_t)) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(RT_ERR_HIP, "the deep Csg units' state: " + std::to_string(need * sizeof(uint32_t)) + " bytes for " +
+                                  std::to_string(lanes) + " lanes could not be allocated");
+    }
+    c->deep_cap = need;
+  }
+  out->csg_deep_state = c->d_deep;
+  out->csg_deep_lanes = (uint32_t)lanes;
+  return RT_OK;
+}
+
 // Device-to-host copy of n bytes into caller (pageable) memory, stream-ordered
 // after the work already on `st`: chunks land in two pinned buffers by DMA
 // while the host copies the previous chunk out (a pageable hipMemcpy of a
@@ -157,6 +178,9 @@ int run_render(rt_scene* s, const WfJob& job_in, hipStream_t stream, const Rende
     e = w->wf->render(s->dev, job, stream, sz, s->tune, s->wfs.size() == 1);
     if (job.gen_ev && res) res->gen_ev_recorded = w->wf->gen_event_recorded();
     if (e == hipSuccess) e = hipEventRecord(w->done, stream);
+    if (e == hipErrorOutOfMemory && w->wf->deep_asked())
+      return fail(RT_ERR_HIP, "the deep Csg units' state: " + std::to_string(w->wf->deep_asked()) +
+                                  " bytes for the workspace's lanes could not be allocated");
     if (e != hipSuccess) return fail(RT_ERR_HIP, std::string("wavefront render: ") + hipGetErrorString(e));
     if (!sync) break;
     if (call.lk) call.lk->unlock();

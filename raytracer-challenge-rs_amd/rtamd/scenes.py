@@ -1029,3 +1029,200 @@ def csg_mesh_random(seed, width=24, height=16):
         cx = 2.4 * (0 - (n_trees - 1) / 2.0)
         return w, _camera(width, height, 1.3, (cx + 0.05, 0.1, 0.45), (0.3, 0.2, 2.0)), 4
     return w, _camera(width, height, PI / 3.0, (0.0, 1.5, -6.0), (0, 0.0, 0.5)), 4
+
+
+# ---- Csg trees beyond the caps (deep units: World.upload(deep_csg=True))
+def _glass_material(index, color=(0.05, 0.05, 0.1)):
+    m = rt.Material()
+    m.color = rt.Color(*color)
+    m.diffuse, m.transparency, m.reflective, m.refractive_index = 0.2, 0.9, 0.3, index
+    return m
+
+
+_PIP_FACES = (  # (axis, sign, pips in the face's own two coordinates): opposite faces sum to 7
+    (1, 1.0, ((0.0, 0.0),)),
+    (0, 1.0, ((-0.5, -0.5), (0.5, 0.5))),
+    (2, 1.0, ((-0.5, -0.5), (0.0, 0.0), (0.5, 0.5))),
+    (2, -1.0, ((-0.5, -0.5), (-0.5, 0.5), (0.5, -0.5), (0.5, 0.5))),
+    (0, -1.0, ((-0.5, -0.5), (-0.5, 0.5), (0.0, 0.0), (0.5, -0.5), (0.5, 0.5))),
+    (1, -1.0, ((-0.5, -0.5), (-0.5, 0.0), (-0.5, 0.5), (0.5, -0.5), (0.5, 0.0), (0.5, 0.5))),
+)
+
+
+def csg_die21(place, material, glass_pips=0, node_transform_every=0, pip=0.17):
+    """The book's die: a cube minus its 21 pips, the pips a left chain of unions (small spheres centred on
+    the six faces). 22 leaves under 21 Csg nodes, 21 levels: beyond every cap. `place` moves every leaf.
+    glass_pips = k > 0: every k-th pip is of glass (index 1.33). node_transform_every = k > 0: every k-th
+    node of the chain carries a small transform of its own (the Csg's box is then tested against the local
+    ray, csg.rs:115-118, a quirk a small move survives)."""
+    cube = rt.Cube()
+    cube.set_transform(place)
+    cube.set_material(material)
+    pips = []
+    for axis, sign, spots in _PIP_FACES:
+        others = [a for a in range(3) if a != axis]
+        for u, v in spots:
+            c = [0.0, 0.0, 0.0]
+            c[axis] = sign
+            c[others[0]], c[others[1]] = u, v
+            s = rt.Sphere()
+            s.set_transform(place * rt.translation(*c) * rt.scaling(pip, pip, pip))
+            k = len(pips)
+            if glass_pips and k % glass_pips == glass_pips - 1:
+                s.set_material(_glass_material(1.33))
+            else:
+                m = rt.Material()
+                m.color = rt.Color(0.95, 0.95, 0.9)
+                s.set_material(m)
+            pips.append(s)
+    chain = pips[0]
+    for k, s in enumerate(pips[1:], 1):
+        chain = rt.Csg(rt.Operation.Union, chain, s)
+        if node_transform_every and k % node_transform_every == 0:
+            chain.set_transform(rt.translation(0.004, -0.003, 0.002) * rt.rotation_y(0.01) * rt.scaling(1.01, 0.99, 1.0))
+    return rt.Csg(rt.Operation.Difference, cube, chain)
+
+
+def csg_row(n, step=0.3, radius=0.5):
+    """A left chain of unions over `n` overlapping spheres along z: sphere k at translation(0, 0, step k) .
+    scaling(radius), every third one of glass with index 1.2 + 0.01 k. n leaves, n - 1 Csg nodes and levels."""
+    row = None
+    for k in range(n):
+        s = rt.Sphere()
+        s.set_transform(rt.translation(0.0, 0.0, step * k) * rt.scaling(radius, radius, radius))
+        if k % 3 == 0:
+            s.set_material(_glass_material(1.2 + 0.01 * k))
+        else:
+            m = rt.Material()
+            m.color = rt.Color(0.3 + 0.6 * ((k * 7) % 10) / 10.0, 0.5, 0.9 - 0.6 * ((k * 3) % 10) / 10.0)
+            s.set_material(m)
+        row = s if row is None else rt.Csg(rt.Operation.Union, row, s)
+    return row
+
+
+def csg_deep_random(seed, width=24, height=16, info=None):
+    """csg_random beyond the caps: a floor, two plain glass spheres and two trees of 5 to 10 levels and 18
+    to 60 leaves each. A tree is a left chain of unions over clusters, a cluster a left chain of unions
+    over parts, a part a small difference or intersection of two or three overlapping leaves, so no
+    operation near the root can empty the tree. Some union nodes carry a small transform of their own;
+    the second tree sits in a group; the first part of every tree has a group for an operand; glass and
+    mirrors among the leaves. `info`: a list that receives each tree's (levels, leaves)."""
+    rng = SplitMix64(0xC5620000 ^ seed)
+    w = rt.World()
+    floor = rt.Plane()
+    floor.set_transform(rt.translation(0, -1.2, 0))
+    floor.material.color = rt.Color(0.7, 0.7, 0.6)
+    floor.material.reflective = 0.25 * rng.u()
+    w.add_object(floor)
+    for k in range(2):
+        s = rt.glass_sphere()
+        r = 0.3 + 0.3 * rng.u()
+        s.set_transform(rt.translation(-3.4 + 6.8 * k + 0.4 * rng.u(), -0.4 + rng.u(), 1.0 * rng.u()) * rt.scaling(r, r, r))
+        s.material.refractive_index = 1.2 + 0.6 * rng.u()
+        s.material.reflective = 0.3
+        w.add_object(s)
+
+    def leaf(x, y, z, size):
+        kind = int(rng.u() * 4)
+        s = (rt.Sphere(), rt.Cube(), rt.Cylinder(-1.0, 1.0, True), rt.Cone(-1.0, 0.0, True))[kind]
+        sc = [size * (0.8 + 0.4 * rng.u()) for _ in range(3)]
+        s.set_transform(rt.translation(x, y, z) * rt.rotation_y(PI * rng.u()) * rt.rotation_x(PI * rng.u()) * rt.scaling(*sc))
+        s.material.color = rt.Color(rng.u(), rng.u(), rng.u())
+        style = rng.u()
+        if style < 0.3:
+            s.material.transparency = 0.5 + 0.5 * rng.u()
+            s.material.refractive_index = 1.1 + 0.9 * rng.u()
+            s.material.reflective = 0.5 * rng.u()
+            s.material.diffuse = 0.3
+        elif style < 0.5:
+            s.material.reflective = 0.2 + 0.6 * rng.u()
+        if rng.u() < 0.1:
+            s.no_shadow()
+        return s
+
+    info = [] if info is None else info
+
+    def part(x, y, z, n_leaves, grouped):
+        """a body with one or two smaller shapes cut out of it or cut to them: 1 or 2 levels"""
+        body = leaf(x, y, z, 0.42)
+        if grouped:  # a group of two shapes for the body (a group inside a tree)
+            g = rt.Group()
+            g.add_child(body)
+            g.add_child(leaf(x + 0.2, y, z, 0.3))
+            body = g
+            n_leaves -= 1
+        cut = leaf(x + 0.25 * (rng.u() - 0.5), y + 0.3, z - 0.25, 0.3)
+        if n_leaves >= 3:
+            cut = rt.Csg(rt.Operation.Union, cut, leaf(x + 0.25 * (rng.u() - 0.5), y - 0.3, z - 0.25, 0.28))
+        op = rt.Operation.Difference if rng.u() < 0.65 else rt.Operation.Intersection
+        return rt.Csg(op, body, cut), (2 if n_leaves >= 3 else 1)
+
+    def nudge(c):
+        c.set_transform(rt.translation(0.03 * (rng.u() - 0.5), 0.03 * (rng.u() - 0.5), 0.0) * rt.rotation_y(0.06 * (rng.u() - 0.5))
+                        * rt.scaling(0.98 + 0.04 * rng.u(), 0.98 + 0.04 * rng.u(), 0.98 + 0.04 * rng.u()))
+
+    def tree(cx, cz):
+        n_clusters = 3 + int(rng.u() * 3)
+        per = 3 + int(rng.u() * (2 if n_clusters == 5 else 3))
+        levels, leaves, root = 0, 0, None
+        for c in range(n_clusters):
+            cluster, deepest = None, 0
+            for p in range(per):
+                n_leaves = 2 + int(rng.u() * 2)
+                ang = 2.0 * PI * (c * per + p) / (n_clusters * per)
+                q, d = part(cx + 0.9 * math.cos(ang) * (0.4 + 0.6 * rng.u()), 0.9 * (rng.u() - 0.4),
+                            cz + 0.9 * math.sin(ang) * (0.4 + 0.6 * rng.u()), n_leaves, c == 0 and p == 0)
+                leaves += n_leaves
+                deepest = 1 + max(deepest, d) if cluster is not None else d
+                cluster = q if cluster is None else rt.Csg(rt.Operation.Union, cluster, q)
+                if cluster is not q and rng.u() < 0.2:
+                    nudge(cluster)
+            levels = 1 + max(levels, deepest) if root is not None else deepest
+            root = cluster if root is None else rt.Csg(rt.Operation.Union, root, cluster)
+            if root is not cluster and rng.u() < 0.3:
+                nudge(root)
+        info.append((levels, leaves))
+        return root
+
+    for k in range(2):
+        cx = 2.6 * (k - 0.5)
+        t = tree(cx, 0.8)
+        if k == 1:
+            g = rt.Group()
+            g.add_child(t)
+            g.add_child(leaf(cx, 0.2, 3.2, 0.5))
+            w.add_object(g)
+        else:
+            w.add_object(t)
+    w.add_light(rt.PointLight(rt.Point(-5, 8, -7), rt.Color(0.9, 0.9, 0.9)))
+    w.add_light(rt.PointLight(rt.Point(6, 5, -4), rt.Color(0.4, 0.4, 0.4)))
+    return w, _camera(width, height, PI / 3.0, (0.0, 1.8, -6.5), (0, 0.0, 0.8)), 4
+
+
+def csg_dice21(n=16, width=640, height=360, seed=0x5EED0C5A, depth=5):
+    """csg_dice with the book's dice (csg_die21: 22 leaves, 21 levels, deep units), for measurements."""
+    rng = SplitMix64(seed)
+    w = rt.World()
+    floor = rt.Plane()
+    floor.material.color = rt.Color(0.8, 0.8, 0.85)
+    floor.material.reflective = 0.2
+    floor.material.specular = 0.0
+    w.add_object(floor)
+    side = max(1, int(math.ceil(math.sqrt(n))))
+    for k in range(n):
+        gx, gz = k % side, k // side
+        s = 0.35 + 0.15 * rng.u()
+        place = (rt.translation(1.6 * (gx - (side - 1) / 2.0) + 0.3 * (rng.u() - 0.5), s,
+                                1.6 * gz + 0.3 * (rng.u() - 0.5))
+                 * rt.rotation_y(PI * rng.u()) * rt.scaling(s, s, s))
+        m = rt.Material()
+        m.color = rt.Color(0.2 + 0.8 * rng.u(), 0.2 + 0.8 * rng.u(), 0.2 + 0.8 * rng.u())
+        if k % 3 == 1:
+            m = _glass_material(1.3 + 0.4 * rng.u())
+        elif k % 3 == 2:
+            m.reflective = 0.6
+        w.add_object(csg_die21(place, m, glass_pips=4 if k % 3 == 1 else 0))
+    w.add_light(rt.PointLight(rt.Point(-6, 9, -8), rt.Color(1.0, 1.0, 1.0)))
+    w.add_light(rt.PointLight(rt.Point(7, 6, -3), rt.Color(0.35, 0.35, 0.35)))
+    reach = 0.8 * side
+    return w, _camera(width, height, PI / 3.0, (0.0, 1.2 + 0.9 * reach, -2.5 - 1.2 * reach), (0, 0.3, 0.8 * reach)), depth
