@@ -10,6 +10,7 @@
 //    program's own (dynamic header included).
 //  - run_tokens on runs of 1-600 bytes against deflate_rle restated serially, whole and in
 //    every split into two parts, and in chunks as the device kernel walks them.
+// `deflate_check lens` instead prints dynamic_len and stored_len for filtered bytes it reads.
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -228,7 +229,23 @@ static std::vector<std::pair<uint32_t, uint32_t>> rle_serial(uint32_t L) {
   return t;
 }
 
-int main() {
+// `deflate_check lens`: every line of the standard input is a segment's filtered bytes in hex;
+// prints "<dynamic_len> <stored_len>" for each, the two sides of the encoders' decision. It
+// labels inputs for tests/test_png_deflate.py's tie canvases; it checks nothing itself.
+static int print_lens() {
+  char line[4096];
+  while (std::fgets(line, sizeof line, stdin)) {
+    std::vector<uint8_t> F;
+    unsigned v;
+    for (const char* p = line; std::sscanf(p, "%2x", &v) == 1; p += 2) F.push_back((uint8_t)v);
+    if (F.empty()) continue;
+    std::printf("%zu %llu\n", deflate_segment(F, true).size(), (unsigned long long)stored_len(F.size()));
+  }
+  return fails ? 1 : 0;
+}
+
+int main(int argc, char** argv) {
+  if (argc > 1 && std::strcmp(argv[1], "lens") == 0) return print_lens();
   std::mt19937_64 rng(20240611);
   {  // Fibonacci-like counts: an unlimited code would be 20+ bits deep
     std::vector<uint32_t> fib(286, 0);

@@ -3,13 +3,19 @@ render-to-compressed-PNG entry point (rt_render_png_deflate).
 
 The format is one fixed file per canvas, so the device encoder must write the host
 encoder's bytes (themselves held to png_deflate_ref.py's checker by test_png_deflate.py):
-on the format's edges, a 640x360 frame of noise, and golden canvases; without touching a
-byte past the file. The render call must equal the host encoder applied to the rendered
-canvas and decode to the oracle's quantised frame; render_png and `render_scene <scene>
-<out>` still give the stored file, and `--compress` the compressed one.
+on the format's edges (png_deflate_ref.edge_canvases: codes cut at 15 and 7 bits, 513 segments,
+the widest row, the tie between the two block forms, ...), over a sweep of widths, on a 640x360
+frame of noise, and on golden canvases; without touching a byte past the file. A camera wider
+than the device encoder's row is refused before it is rendered. The render call must equal the
+host encoder applied to the rendered canvas and decode to the oracle's quantised frame;
+render_png and `render_scene <scene> <out>` still give the stored file, and `--compress` the
+compressed one (4000 segments: a file zlib inflates, with chunk CRCs that hold).
 """
+import ctypes
+import math
 import os
 import subprocess
+import zlib
 
 import numpy as np
 import pytest
@@ -56,6 +62,15 @@ def test_device_equals_host_on_format_edges(rt, name):
     _check(rt, ref.edge_canvases()[name])
 
 
+@pytest.mark.parametrize("w", ref.sweep_widths())
+def test_device_equals_host_over_widths(rt, w):
+    """Five rows of every width of the sweep (1..48, rows that cross 256, 512 and 1024 bytes, a width
+    for every number of bytes a thread can own): where rows and runs fall in the threads' chunks and
+    which threads own nothing follows from the width. test_png_deflate.py holds the host's files of
+    the same canvases to the block checker and counts their block forms and matches."""
+    _check(rt, ref.sweep_canvas(w))
+
+
 def test_device_equals_host_on_a_frame(rt):
     _check(rt, png_ref.sized_canvas("frame_640x360"))
 
@@ -95,6 +110,37 @@ def test_device_buffer_conventions_and_refused_sizes(rt):
             rt._rtamd.canvas_to_png_deflate_device(d.data_ptr(), bw, bh, 0, 0, 0)
     with pytest.raises(rt.RtError, match="wider"):  # a row beyond the workgroup's LDS: the host encoder takes it
         rt._rtamd.canvas_to_png_deflate_device(d.data_ptr(), 8534, 1, out.data_ptr(), len(want), 0)
+
+
+def test_render_png_deflate_refuses_a_wider_row(rt):
+    """A camera one pixel wider than the device encoder's row: the size query still answers with the
+    bound, the render call is refused before anything is rendered or written."""
+    from rtamd import scenes
+    w, cam, depth = scenes.first_scene(16, 9)
+    cam.render(w, depth, want_stats=False)  # (the scene is on the device from here on)
+    wide = rt.Camera(ref.DEVICE_MAX_WIDTH + 1, 1, math.pi / 3)
+    lib = ctypes.CDLL(rt.LIB_PATH)
+    lib.rt_render_png_deflate.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint32, ctypes.c_uint32,
+                                          ctypes.c_void_p, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t),
+                                          ctypes.c_void_p]
+    lib.rt_last_error.restype = ctypes.c_char_p
+    bound, n = ref.bound(ref.DEVICE_MAX_WIDTH + 1, 1), ctypes.c_size_t(0)
+    assert lib.rt_render_png_deflate(w._scene_handle(), wide.desc_bytes(), depth, 1, None, 0, ctypes.byref(n), None) == 0
+    assert n.value == bound == rt._rtamd.png_deflate_bound(ref.DEVICE_MAX_WIDTH + 1, 1)
+    out = ctypes.create_string_buffer(bytes([POISON]) * bound, bound)
+    stats = ctypes.create_string_buffer(bytes([POISON]) * 256, 256)  # (rt_stats is smaller)
+    assert lib.rt_render_png_deflate(w._scene_handle(), wide.desc_bytes(), depth, 1, out, bound, ctypes.byref(n),
+                                     stats) == -1  # RT_ERR_INVALID_ARGUMENT
+    assert "wider" in lib.rt_last_error().decode()
+    assert out.raw == bytes([POISON]) * bound and stats.raw == bytes([POISON]) * 256
+    with pytest.raises(rt.RtError, match="wider"):
+        wide.render_png_deflate(w, depth)
+    # the widest camera it takes
+    widest = rt.Camera(ref.DEVICE_MAX_WIDTH, 1, math.pi / 3)
+    png, _ = widest.render_png_deflate(w, depth)
+    canvas, _ = widest.render(w, depth, want_stats=False)
+    assert png == rt.canvas_to_png_deflate(canvas.to_numpy())
+    w.check()
 
 
 def _cover_80x80(tmp_path):
@@ -174,6 +220,10 @@ def test_render_scene_cli_compress_flag(rt, tmp_path):
     lib_out = tmp_path / "lib.png"
     p.render_to(str(lib_out), 5, True)
     assert lib_out.read_bytes() == out.read_bytes()
+    # 4000 segments the device agrees with itself on: the chunk CRCs hold, and zlib inflates the rows (the Adler-32)
+    parts = ref.chunks(out.read_bytes())
+    assert [k for k, _ in parts] == [b"IHDR", b"IDAT", b"IEND"] and ref.n_segments(4000, 4000) == 4000
+    assert len(zlib.decompress(parts[1][1])) == 4000 * (3 * 4000 + 1)
     _, small = _cover_80x80(tmp_path)
     p80 = rt.SceneParser()
     p80.load_file(str(small))

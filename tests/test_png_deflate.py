@@ -1,8 +1,13 @@
 """The compressed PNG writer on the host (rt_canvas_to_png_deflate, rt_png_deflate_bound,
 Canvas.to_png_deflate / save_compressed) against png_deflate_ref.py's checker, which is
 built from the format alone: chunk CRCs, zlib's inflate, the minimum-sum filter rule
-recomputed in numpy, PIL's pixels, and the size against zlib's Z_RLE strategy on the golden
-frames; the format's edges; the buffer conventions; the stored encoder's unchanged bytes;
+recomputed in numpy, PIL's pixels, every block read by a bit reader from RFC 1951 (the block
+layout, deflate_rle's tokens, codes of minimum-redundancy cost), and the size against zlib's
+Z_RLE strategy on the golden frames; the format's edges, each asserted to reach its regime (codes
+cut at 15 and at 7 bits, 513 segments, the widest row the device takes, a tie between the two
+block forms, a row over a stored block); the width sweep of the device tests; the block checker
+itself on streams built here, which it must accept or reject; the buffer conventions; the stored
+encoder's unchanged bytes;
 and the shared arithmetic (csrc/rt_png_deflate.hpp: code lengths, canonical codes, the bit
 writer, the run tokeniser) in a stand-alone program built with the address and
 undefined-behaviour sanitizers (tests/cpp/deflate_check.cpp)."""
@@ -45,25 +50,27 @@ def _bound(rt, w, h):
     return b
 
 
-def _host(rt, oracle, canvas, size_against_rle=False):
-    """The binding's file through the checker; the C entry point writes the same bytes."""
+def _host(rt, oracle, canvas, size_against_rle=False, sample=None):
+    """The binding's file through the checker, every block included (of segments_513, `sample`'s);
+    the C entry point writes the same bytes. Returns the file, its filtered bytes and its segments."""
     h, w = canvas.shape[0], canvas.shape[1]
     png = rt.canvas_to_png_deflate(canvas)
     px = png_ref.quantised(oracle, canvas)
-    idat, F = ref.check_file(png, px, size_against_rle, bound_of=lambda w, h: _bound(rt, w, h))
+    idat, F, segs = ref.check_file(png, px, size_against_rle, bound_of=lambda w, h: _bound(rt, w, h), blocks=True,
+                                   sample=sample)
     lib = _c_api()
     canvas = np.ascontiguousarray(canvas, dtype=np.float64)
     buf = ctypes.create_string_buffer(len(png))
     n = ctypes.c_size_t(0)
     assert lib.rt_canvas_to_png_deflate(canvas.ctypes.data, w, h, buf, len(png), ctypes.byref(n)) == 0
     assert n.value == len(png) and buf.raw == png
-    return png, F
+    return png, F, segs
 
 
 @pytest.mark.parametrize("name", GOLDEN_NAMES)
 def test_golden_frames(rt, oracle, name):
     canvas = np.load(os.path.join(GOLDEN, name + ".npz"))["canvas"]
-    png, _ = _host(rt, oracle, canvas, size_against_rle=True)
+    png, _, _ = _host(rt, oracle, canvas, size_against_rle=True)
     if name in ref.GOLDEN_HALF:
         assert 2 * len(png) < rt._rtamd.png_size(canvas.shape[1], canvas.shape[0])
 
@@ -72,12 +79,41 @@ def test_golden_frames_are_all_there():
     assert set(ref.GOLDEN_HALF) <= set(GOLDEN_NAMES) and len(GOLDEN_NAMES) >= 18
 
 
-@pytest.mark.parametrize("name", ref.EDGE_NAMES)
+@pytest.mark.parametrize("name", ref.HOST_NAMES)
 def test_format_edges(rt, oracle, name):
     canvas = ref.edge_canvases()[name]
     h, w = canvas.shape[0], canvas.shape[1]
-    png, F = _host(rt, oracle, canvas)
+    png, F, segs = _host(rt, oracle, canvas, sample=ref.SEGMENTS_513_SAMPLE if name == "segments_513" else None)
+    kinds = [s["kind"] for s in segs]
     first_block = png[43]  # the byte after 78 01: BFINAL, BTYPE
+    if name.startswith("lit_limit_"):  # a minimum-redundancy code would be deeper than 15 bits
+        counts = np.bincount(np.frombuffer(F, np.uint8), minlength=257)
+        counts[256] = 1
+        assert (w, F[0], kinds) == ({"16": 1393, "18": 3648}[name[10:]], 0, ["dynamic"]) and ref.longest_run(F) <= 2
+        assert ref.huffman_cost_and_depth(counts)[1] == int(name[10:]) > 15
+        assert max(segs[0]["ll_lens"]) == 15 and ref.check_segment(segs[0], F)[0] == int(name[10:])
+    if name == "cl_limit":  # the lengths the header sends want a code-length code deeper than 7 bits
+        sent = np.bincount(segs[0]["sent"], minlength=19).tolist()
+        assert (w, F[0], kinds) == (682, 0, ["dynamic"]) and ref.longest_run(F) <= 2
+        assert sent == [170, 0, 0] + [ref.CL_LIMIT_LENGTHS[l] for l in range(3, 12)] + [0] * 7
+        assert ref.huffman_cost_and_depth(sent)[1] == 9 > 7 and max(segs[0]["cl_lens"]) == 7
+    if name == "segments_513":  # more than two rounds of 256 segments, of both forms and many lengths
+        assert ref.n_segments(w, h) == 513 == len(segs) and ref.rows_per_segment(w) == 1
+        assert kinds.count("dynamic") > 100 and kinds.count("stored") > 100
+        assert {"dynamic", "stored"} <= {kinds[k] for k in ref.SEGMENTS_513_SAMPLE}
+        assert len({s["bytes"][1] - s["bytes"][0] for s in segs}) > 100
+    if name in ("max_width", "max_width_minus_1", "row_of_a_segment"):  # noise, then a row that shrinks
+        assert w == {"max_width": ref.DEVICE_MAX_WIDTH, "max_width_minus_1": ref.DEVICE_MAX_WIDTH - 1}.get(name, 5461)
+        assert kinds == ["stored", "dynamic"] and segs[0]["bytes"] == (2, 2 + 3 * w + 1 + 5)
+        assert 3 * w + 1 == {"max_width": 256 * 100, "max_width_minus_1": 256 * 100 - 3}.get(name, ref.SEGMENT)
+        assert len(segs[1]["tokens"]) > 2000
+    if name == "row_over_stored_block":  # a row longer than a stored block, and than the device takes
+        assert 3 * w + 1 == 65539 and w > ref.DEVICE_MAX_WIDTH and kinds == ["stored", "dynamic"]
+        assert segs[0]["blocks"] == [65535, 4] and len(segs[1]["raw"]) > 65535
+    if name == "wins_by_one":  # the dynamic form wins by the least there is
+        assert kinds == ["dynamic"] and segs[0]["bytes"] == (2, 2 + len(F) + 4) and ref.stored_len(len(F)) == len(F) + 5
+    if name == "tie":  # (test_tie_is_a_tie: the dynamic form would be exactly as long)
+        assert kinds == ["stored"] and segs[0]["bytes"] == (2, 2 + len(F) + 5)
     if name.startswith("run_"):
         assert ref.longest_run(F) == int(name[4:]) and F[0] == 0
     if name == "all_ones":
@@ -95,7 +131,200 @@ def test_format_edges(rt, oracle, name):
         assert (first_block >> 3 | (png[44] & 3) << 5) & 31 == 0  # HLIT 257: no length symbol has a code
 
 
-@pytest.mark.parametrize("name", ref.EDGE_NAMES)
+def test_width_sweep_on_the_host(rt, oracle):
+    """The device tests' width sweep (test_gpu_png_deflate.py) through the host encoder and the block
+    checker; over the sweep both block forms occur, matches of 258 bytes and shorter ones."""
+    widths = ref.sweep_widths()
+    assert set(range(1, 49)) | {84, 85, 86, 170, 171, 341, 342} <= set(widths)
+    assert {ref.device_chunk(w) for w in widths} == {ref.device_chunk(w) for w in range(1, ref.DEVICE_MAX_WIDTH + 1)}
+    kinds, lengths = set(), set()
+    for w in widths:
+        canvas = ref.sweep_canvas(w)
+        assert canvas.shape == (ref.SWEEP_H, w, 3)
+        _, _, segs = ref.check_file(rt.canvas_to_png_deflate(canvas), png_ref.quantised(oracle, canvas), blocks=True)
+        kinds |= {s["kind"] for s in segs}
+        lengths |= {t[0] for s in segs if s["kind"] == "dynamic" for t in s["tokens"] if isinstance(t, tuple)}
+    assert kinds == {"dynamic", "stored"}
+    assert 258 in lengths and len(lengths - {258}) > 20
+
+
+# ---- the block checker itself, on streams built here
+class _BitsOut:
+    def __init__(self):
+        self.bits = []
+
+    def put(self, v, n):  # a number: least significant bit first
+        self.bits.extend((v >> i) & 1 for i in range(n))
+
+    def code(self, v, n):  # a Huffman code: most significant bit first
+        self.bits.extend((v >> i) & 1 for i in reversed(range(n)))
+
+    def pad(self):
+        self.bits.extend([0] * (-len(self.bits) % 8))
+
+    def bytes(self):
+        return np.packbits(np.array(self.bits, np.uint8), bitorder="little").tobytes()
+
+
+def _canonical(lens):  # RFC 1951 3.2.2
+    codes, code = {}, 0
+    for l in range(1, max(lens) + 1):
+        for s, sl in enumerate(lens):
+            if sl == l:
+                codes[s] = code
+                code += 1
+        code <<= 1
+    return codes
+
+
+def _huffman_lengths(counts):
+    """Code lengths of a Huffman code without a length limit (two symbols at the least)."""
+    import heapq
+    heap = [(c, [s]) for s, c in enumerate(counts) if c]
+    lens = [0] * len(counts)
+    heapq.heapify(heap)
+    while len(heap) > 1:
+        a, sa = heapq.heappop(heap)
+        b, sb = heapq.heappop(heap)
+        for s in sa + sb:
+            lens[s] += 1
+        heapq.heappush(heap, (a + b, sa + sb))
+    return lens
+
+
+def _counts(toks):
+    counts = [0] * 286
+    for t in toks:
+        counts[ref.length_symbol(t[0])[0] if isinstance(t, tuple) else t] += 1
+    counts[256] = 1
+    return counts
+
+
+def _dynamic_segment(toks, ll_lens=None, last=True, hlit=None, zero_run=False):
+    """A dynamic block of `toks` and the closing empty stored block, as the format lays a segment
+    out; with Huffman lengths, or with ll_lens; HLIT the least or `hlit`; `zero_run`: the header
+    sends its first three or more zeros in a row as one code 17 or 18."""
+    ll_lens = ll_lens or _huffman_lengths(_counts(toks))
+    matches = any(isinstance(t, tuple) for t in toks)
+    hlit = hlit or max([257] + [s + 1 for s in range(257, 286) if ll_lens[s]])
+    sent = ll_lens[:hlit] + [1 if matches else 0]
+    if zero_run:
+        at = next(i for i in range(len(sent) - 2) if sent[i:i + 3] == [0, 0, 0])
+        zeros = min(138, next(i for i in range(at, len(sent) + 1) if i == len(sent) or sent[i]) - at)
+        sent[at:at + zeros] = [(17 if zeros < 11 else 18, zeros)]
+    cl_counts = [0] * 19
+    for s in sent:
+        cl_counts[s[0] if isinstance(s, tuple) else s] += 1
+    cl_lens = _huffman_lengths(cl_counts)
+    assert max(cl_lens) <= 7 and max(ll_lens) <= 15
+    hclen = max([4] + [i + 1 for i in range(19) if cl_lens[ref.CL_ORDER[i]]])
+    o, ll, cl = _BitsOut(), _canonical(ll_lens), _canonical(cl_lens)
+    o.put(0, 1), o.put(2, 2), o.put(hlit - 257, 5), o.put(0, 5), o.put(hclen - 4, 4)
+    for i in range(hclen):
+        o.put(cl_lens[ref.CL_ORDER[i]], 3)
+    for s in sent:
+        if isinstance(s, tuple):
+            o.code(cl[s[0]], cl_lens[s[0]]), o.put(s[1] - (3 if s[0] == 17 else 11), 3 if s[0] == 17 else 7)
+        else:
+            o.code(cl[s], cl_lens[s])
+    for t in toks:
+        if isinstance(t, tuple):
+            sym, extra = ref.length_symbol(t[0])
+            o.code(ll[sym], ll_lens[sym]), o.put(t[0] - ref._LEN_BASE[sym - 257], extra), o.put(0, 1)
+        else:
+            o.code(ll[t], ll_lens[t])
+    o.code(ll[256], ll_lens[256])
+    o.put(1 if last else 0, 1), o.put(0, 2), o.pad(), o.put(0, 16), o.put(0xFFFF, 16)
+    return o.bytes()
+
+
+def _payload(F, segment):
+    import zlib
+    z = b"\x78\x01" + segment + zlib.adler32(F).to_bytes(4, "big")
+    assert zlib.decompress(z) == F  # (every stream here is a valid one)
+    return z
+
+
+CHECKER_ROW = bytes([0] + [7] * 300 + [9] * 5 + [7, 8] * 10 + [1, 2, 3, 3, 3, 4, 4, 4, 4] + list(range(100, 159)))  # W 131
+
+
+def test_block_checker_accepts_a_hand_built_segment():
+    F = CHECKER_ROW
+    toks = ref.tokens(F)
+    assert toks[:5] == [0, 7, (258, 1), (41, 1), 9] and toks[5:7] == [(4, 1), 7] and (3, 1) in toks and [3, 3, 3] == toks[28:31]
+    assert ref.expand(toks) == F
+    segs = ref.check_blocks(_payload(F, _dynamic_segment(toks)), F, (len(F) - 1) // 3, 1)
+    assert [s["kind"] for s in segs] == ["dynamic"] and segs[0]["tokens"] == toks
+    stored = b"\x01" + len(F).to_bytes(2, "little") + (len(F) ^ 0xFFFF).to_bytes(2, "little") + F
+    assert ref.check_blocks(_payload(F, stored), F, (len(F) - 1) // 3, 1)[0]["blocks"] == [len(F)]
+
+
+@pytest.mark.parametrize("what, says", [("lengths", "minimum-redundancy"), ("tokens", "deflate_rle"),
+                                        ("literals", "deflate_rle"), ("hlit", "HLIT"), ("run_code", "run code"),
+                                        ("bfinal", "BFINAL"), ("fixed", "fixed-Huffman")])
+def test_block_checker_rejects(what, says):
+    """Streams zlib inflates to the right bytes, which are not the format's: a complete code that is not
+    a minimum-redundancy one (two symbols' lengths swapped), other tokens (a match of 258 split in
+    two; a run as literals), an HLIT above the least, a run code in the header, a final bit that is
+    missing, a fixed-Huffman block."""
+    import zlib
+    F = CHECKER_ROW
+    toks = ref.tokens(F)
+    if what == "lengths":
+        lens = _huffman_lengths(_counts(toks))
+        assert lens[7] < lens[100]
+        lens[7], lens[100] = lens[100], lens[7]
+        seg = _dynamic_segment(toks, ll_lens=lens)
+    elif what == "tokens":
+        seg = _dynamic_segment(toks[:2] + [(129, 1), (129, 1)] + toks[3:])
+    elif what == "literals":
+        seg = _dynamic_segment(toks[:5] + [9] * 4 + toks[6:])
+    elif what == "hlit":  # (CHECKER_ROW's match of 258 takes the last length symbol: a row without one)
+        F = bytes([0] + [7] * 9 + [1, 2, 3])
+        toks = ref.tokens(F)
+        assert toks == [0, 7, (8, 1), 1, 2, 3]
+        seg = _dynamic_segment(toks, hlit=264)
+    elif what == "run_code":
+        seg = _dynamic_segment(toks, zero_run=True)
+    elif what == "bfinal":
+        seg = _dynamic_segment(toks, last=False)
+    else:
+        co = zlib.compressobj(6, zlib.DEFLATED, -15, 8, zlib.Z_FIXED)
+        seg = co.compress(F) + co.flush()
+    z = b"\x78\x01" + seg + zlib.adler32(F).to_bytes(4, "big")
+    if what != "bfinal":  # (without a final block zlib reads on past the end)
+        assert zlib.decompress(z) == F
+    with pytest.raises(AssertionError, match=says):
+        ref.check_blocks(z, F, (len(F) - 1) // 3, 1)
+
+
+def test_tokens_are_zlib_rle_tokens():
+    """`tokens` against the tokens in zlib's own Z_RLE output, read with the checker's bit reader."""
+    import zlib
+    rng = np.random.default_rng(1951)
+    cases = [b"a" * n for n in (1, 2, 3, 4, 5, 6, 258, 259, 260, 261, 262, 516, 517, 518, 519, 520, 1000)]
+    cases += [b"ab" * 20 + b"c" * n + b"d" for n in (3, 4, 260, 261)]
+    for _ in range(40):
+        runs = rng.integers(1, [4, 9, 300, 700][int(rng.integers(4))], size=int(rng.integers(1, 40)))
+        cases.append(b"".join(bytes([int(rng.integers(3))]) * int(n) for n in runs))
+    for F in cases:
+        co = zlib.compressobj(6, zlib.DEFLATED, -15, 8, zlib.Z_RLE)
+        got = ref.inflate_tokens(co.compress(F) + co.flush())
+        assert got == ref.tokens(F), F[:40]
+        assert ref.expand(got) == F
+
+
+def test_huffman_cost_and_depth():
+    assert ref.huffman_cost_and_depth([0, 5, 0]) == (5, 1)
+    assert ref.huffman_cost_and_depth([1, 1]) == (2, 1)
+    assert ref.huffman_cost_and_depth([1, 1, 2, 4, 8]) == (1 * 4 + 1 * 4 + 2 * 3 + 4 * 2 + 8, 4)
+    assert ref.huffman_cost_and_depth([1, 1, 1, 1]) == (8, 2)  # (a chain would cost 9)
+    assert ref.huffman_cost_and_depth([1, 1, 2, 2]) == (12, 2)  # the shallower of two codes of equal cost
+    fib = [1, 1, 2, 3, 5, 8, 13, 21, 34, 55, 89, 144, 233, 377, 610, 987, 1597]
+    assert ref.huffman_cost_and_depth(fib)[1] == 16
+
+
+@pytest.mark.parametrize("name", ref.HOST_NAMES)
 def test_stored_encoder_is_unchanged(rt, oracle, name):
     canvas = ref.edge_canvases()[name]
     assert rt.canvas_to_png(canvas) == png_ref.expected_png(png_ref.quantised(oracle, canvas))
@@ -170,3 +399,18 @@ def deflate_check(tmp_path_factory):
 def test_deflate_arithmetic_under_sanitizers(deflate_check):
     r = subprocess.run([deflate_check], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.startswith("OK"), r.stdout + r.stderr
+
+
+def test_tie_is_a_tie(rt, oracle, deflate_check):
+    """The shared header's two lengths for the filtered bytes of `tie` and `wins_by_one` (deflate_check
+    lens only labels the inputs: what the files must be is test_format_edges' business): equal, so
+    that `tie` is stored, and apart by one."""
+    rows = []
+    for name in ("tie", "wins_by_one"):
+        canvas = ref.edge_canvases()[name]
+        _, F = ref.check_file(rt.canvas_to_png_deflate(canvas), png_ref.quantised(oracle, canvas))
+        rows.append(F)
+    r = subprocess.run([deflate_check, "lens"], input="".join(F.hex() + "\n" for F in rows), capture_output=True,
+                       text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert r.stdout.split() == [str(len(rows[0]) + 5), str(len(rows[0]) + 5), str(len(rows[1]) + 4), str(len(rows[1]) + 5)]
