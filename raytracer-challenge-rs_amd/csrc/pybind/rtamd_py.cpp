@@ -92,6 +92,7 @@ extern "C" int rtamd_wf_plan(const rt_scene* s, long long out[16]);
 extern "C" int rtamd_wf_shape(const rt_scene* s, long long out[4]);
 extern "C" int rtamd_csg_plan(const rt_scene* s, long long out[6]);
 extern "C" int rtamd_csg_deep_plan(const rt_scene* s, long long out[5]);
+extern "C" int rtamd_csg_run_plan(const rt_scene* s, long long out[6]);
 extern "C" int rtamd_scene_tuning_set(const rt_scene* s, const char* key, int value);
 extern "C" int rtamd_render_shard_host(const rt_scene* scene, const rt_camera_desc* camera, uint32_t max_depth,
                                        uint32_t aa_samples, uint32_t row_block, uint32_t shard, uint32_t n_shards,
@@ -945,6 +946,16 @@ PYBIND11_MODULE(_rtamd, m) {
     check(rtamd_csg_deep_plan(w.scene(), o), "csg_deep_plan");
     py::dict d;
     d["units"] = o[0]; d["levels"] = o[1]; d["nodes"] = o[2]; d["leaves"] = o[3]; d["lane_bytes"] = o[4];
+    return d;
+  }, py::arg("world"));
+  // the run hierarchies inside the wide and deep Csg units (csg_run_walk): the runs that have one, the
+  // triangles boxed, the remainder, the nodes and the greatest depth; `ran` = the last render walked them
+  m.def("_csg_run_plan", [](const World& w) {
+    long long o[6] = {0};
+    check(rtamd_csg_run_plan(w.scene(), o), "csg_run_plan");
+    py::dict d;
+    d["runs"] = o[0]; d["boxed"] = o[1]; d["remainder"] = o[2];
+    d["nodes"] = o[3]; d["depth"] = o[4]; d["ran"] = o[5] != 0;
     return d;
   }, py::arg("world"));
   m.def("_tuning_set", [](const std::string& k, int v) { check(rtamd_tuning_set(k.c_str(), v), "tuning"); });

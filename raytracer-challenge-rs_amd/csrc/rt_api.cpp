@@ -19,6 +19,13 @@ int g_lb_res = -1;
 // the other hierarchies' kMinHierRecords; profiles/csg_hier_ab.txt)
 constexpr int kCsgHierMinDefault = 16;
 int g_csg_hier_min = kCsgHierMinDefault;
+// boxed triangles of a run of triangle leaves inside a wide or deep Csg unit from which the run's
+// hierarchy is built ("csg_run_min"; 0 restores the default, the other hierarchies'
+// kMinHierRecords; 65536 at most, which switches off every run of up to 65535 triangles; a creation knob like
+// csg_hier_min: it is read when a scene is created, so rtamd_scene_tuning_set / World.tune, which act on a scene
+// that exists, do not take it; profiles/csg_run_ab.txt)
+constexpr int kCsgRunMinDefault = 16;
+int g_csg_run_min = kCsgRunMinDefault;
 // every Csg unit through the wide units' streamed evaluator, out of the units' hierarchy
 // ("csg_wide_all": the cross-check of csg_wide_eval against csg_unit_eval; off by default)
 int g_csg_wide_all = 0;
@@ -202,6 +209,20 @@ int rtamd_csg_deep_plan(const rt_scene* cs, long long out[5]) {
   return RT_OK;
 }
 
+// Development hook (not in the public ABI): the run hierarchies inside the wide and deep Csg units
+// (csg_run_walk). out[0..5]: the runs with a hierarchy, the triangles boxed, the remainder (those
+// tri_box refuses, tested by every ray), the nodes, the greatest depth, and whether the last render
+// walked them (any render but an exhaustive one, with `accel` on, of a scene that has one).
+int rtamd_csg_run_plan(const rt_scene* cs, long long out[6]) {
+  if (!cs || !out) return fail(RT_ERR_INVALID_ARGUMENT, "null scene or output");
+  rt_scene* s = const_cast<rt_scene*>(cs);
+  std::lock_guard<std::mutex> lk(s->mu);
+  out[0] = s->dev.n_csg_runs;
+  for (int k = 0; k < 4; ++k) out[1 + k] = s->csg_run_plan[k];
+  out[5] = s->last_wf && s->last_wf->wf->runs_walked() ? 1 : 0;
+  return RT_OK;
+}
+
 // Rays of each generation of the scene's last render (dev tool): returns the
 // number of generations written into out[0 .. max).
 int rtamd_wf_gen_counts(const rt_scene* cs, unsigned* out, int max) {
@@ -218,7 +239,7 @@ int rtamd_wf_gen_counts(const rt_scene* cs, unsigned* out, int max) {
 }
 
 // Development-only tuning hooks (not declared in include/rt_render.h).
-// rtamd_tuning_set: the scene-creation knobs (lb_res, bvh_leaf, bvh_ct, csg_hier_min) and
+// rtamd_tuning_set: the scene-creation knobs (lb_res, bvh_leaf, bvh_ct, csg_hier_min, csg_run_min) and
 // the render-time defaults copied into scenes created afterwards;
 // rtamd_scene_tuning_set: one scene's render-time knobs (WfTuning).
 int rtamd_tuning_set(const char* key, int value) {
@@ -242,6 +263,12 @@ int rtamd_tuning_set(const char* key, int value) {
     if (value < 0 || value > 65536)
       return fail(RT_ERR_INVALID_ARGUMENT, "csg_hier_min must be in [1, 65536], or 0 for the default");
     g_csg_hier_min = value ? value : kCsgHierMinDefault;
+    return RT_OK;
+  }
+  if (key && std::strcmp(key, "csg_run_min") == 0) {
+    if (value < 0 || value > 65536)
+      return fail(RT_ERR_INVALID_ARGUMENT, "csg_run_min must be in [1, 65536], or 0 for the default");
+    g_csg_run_min = value ? value : kCsgRunMinDefault;
     return RT_OK;
   }
   if (key && std::strcmp(key, "csg_wide_all") == 0) {

@@ -51,6 +51,7 @@ extern int g_bvh_leaf;  // BVH leaf size; 0 = automatic: 2, or 1 when the LDS im
 extern int g_bvh_ct;    // SAH node-visit cost in percent of a sphere test
 extern int g_lb_res;    // light-buffer cells per cube-map face edge: 0 = none, -1 = by scene size
 extern int g_csg_hier_min;  // boxed Csg units from which their hierarchy is built
+extern int g_csg_run_min;   // boxed triangles of a run inside a wide or deep Csg unit from which its hierarchy is built
 extern int g_csg_wide_all;  // every Csg unit through the wide units' evaluator (development cross-check)
 extern int g_csg_deep_all;  // every Csg unit through the deep units' evaluator (the same; it wins over csg_wide_all)
 // render-time tuning copied into every scene at its creation (rt_scene::tune)
@@ -209,6 +210,7 @@ struct rt_scene {
   std::mutex multi_mu;
   int prof_mask = (1 << WF_NCLASS) - 1;
   int n_objects = 0, n_lights = 0;
+  long long csg_run_plan[4] = {0, 0, 0, 0};   // run hierarchies: triangles boxed, remainder, nodes, greatest depth
   long long csg_deep_plan[4] = {0, 0, 0, 0};  // deep Csg units; the largest one's levels, nodes, leaves of kinds 0-4
   WfTuning tune;  // this scene's render-time tuning (read under `mu` by every render)
   WfSizing sizing;  // the fast path's queue arenas, learned from this scene's frames (under `mu`)

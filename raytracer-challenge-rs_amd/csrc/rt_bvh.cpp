@@ -719,8 +719,12 @@ std::vector<BvhNode> build_line_bvh(std::vector<QuadRec>& recs, std::vector<Cone
 // |d| |e1| |e2| / EPSILON (the reference rejects |det| < EPSILON) and
 // S = |s| + 2 (|e1| + |e2|). tri_trace walks the hierarchy only for rays with
 // |d|_inf <= kTriDirMax and |o|_inf <= kTriOriginMax, which bounds |d| and |s|
-// in object space through the record's inverse A.
-bool tri_box(const TriRec& r, double lo[3], double hi[3]) {
+// in object space through the record's inverse A. The two bounds are parameters: a triangle
+// under a Csg is handed the chained ray, whose bounds are its run's (csg_run_bounds), and the
+// argument speaks only of the ray tri_local_intersect is handed and of the record's inverse.
+bool tri_box(const TriRec& r, double lo[3], double hi[3]) { return tri_box(r, kTriDirMax, kTriOriginMax, lo, hi); }
+bool tri_box(const TriRec& r, double dir_max, double origin_max, double lo[3], double hi[3]) {
+  if (!(dir_max > 0.0) || !(origin_max >= 0.0) || !std::isfinite(dir_max) || !std::isfinite(origin_max)) return false;
   double F[3][3];
   const double cond = invert3(r.m, F);
   if (!(cond <= 1e6)) return false;  // too ill-conditioned for the padding argument
@@ -731,8 +735,8 @@ bool tri_box(const TriRec& r, double lo[3], double hi[3]) {
     for (int j = 0; j < 3; ++j) a_f += r.m[4 * i + j] * r.m[4 * i + j];
   a_f = std::sqrt(a_f);
   const double s3 = std::sqrt(3.0);
-  const double d_max = a_f * s3 * kTriDirMax;
-  const double s_max = a_f * s3 * kTriOriginMax + norm2(b) + norm2(r.p1);
+  const double d_max = a_f * s3 * dir_max;
+  const double s_max = a_f * s3 * origin_max + norm2(b) + norm2(r.p1);
   const double ne1 = norm2(r.e1), ne2 = norm2(r.e2);
   const double kappa = d_max * ne1 * ne2 / kEpsilon + 1.0;
   const double eta = 64.0 * 0x1p-53 * kappa * (s_max + 2.0 * (ne1 + ne2));
@@ -768,6 +772,57 @@ std::vector<BvhNode> build_tri_bvh(std::vector<TriRec>& recs, int leaf_size, int
   std::vector<int> order;
   std::vector<BvhNode> nodes = build_over_boxes(boxes, leaf_size, trav_cost, depth, &order);
   if (!nodes.empty()) apply_order(recs, order);
+  return nodes;
+}
+
+// The run hierarchies (rt_layout.hpp CsgRun; DESIGN.md §5.2 "Csg units: run hierarchies").
+// csg_run_bounds: the chained ray below `n` Csg inverses (the outermost first), each applied as
+// Ray::transform applies it, for a world ray within kTriDirMax / kTriOriginMax: |A d|_inf <=
+// |A|_inf |d|_inf and |A o + b|_inf <= |A|_inf |o|_inf + |b|_inf level by level, with a little
+// slack for the roundings. The device tests the chained ray against the stored bounds, so a
+// generous bound costs padding and a tight one fallbacks, neither correctness.
+void csg_run_bounds(const double* const* chain, int n, double* dir_max, double* origin_max) {
+  double dm = kTriDirMax, om = kTriOriginMax;
+  for (int j = 0; j < n; ++j) {
+    const double* m = chain[j];
+    double na = 0.0, nb = 0.0;
+    for (int i = 0; i < 3; ++i) {
+      na = std::max(na, std::fabs(m[4 * i]) + std::fabs(m[4 * i + 1]) + std::fabs(m[4 * i + 2]));
+      nb = std::max(nb, std::fabs(m[4 * i + 3]));
+    }
+    if (!(na == na) || !(nb == nb)) na = nb = INFINITY;  // (max drops a NaN)
+    dm = na * dm * (1.0 + 1e-9);
+    om = (na * om + nb) * (1.0 + 1e-9);
+  }
+  *dir_max = dm;
+  *origin_max = om;
+}
+
+std::vector<BvhNode> build_csg_run(TriRec* recs, int n, double dir_max, double origin_max, int min_boxed, int leaf_size,
+                                   double trav_cost, int* n_boxed, int* depth) {
+  *n_boxed = 0;
+  if (depth) *depth = 0;
+  std::vector<Box> boxes;
+  std::vector<TriRec> boxed, rest;
+  for (int i = 0; i < n; ++i) {
+    Box b;
+    if (tri_box(recs[i], dir_max, origin_max, b.lo, b.hi)) {
+      boxes.push_back(b);
+      boxed.push_back(recs[i]);
+    } else {
+      rest.push_back(recs[i]);
+    }
+  }
+  if (boxed.empty() || (int)boxed.size() < min_boxed) return {};
+  std::vector<int> order;
+  int dep = 0;
+  std::vector<BvhNode> nodes = build_over_boxes(boxes, leaf_size, trav_cost, &dep, &order);
+  if (nodes.empty() || dep > kBvhMaxDepth) return {};  // none, or deeper than csg_run_walk's stack: one by one
+  apply_order(boxed, order);
+  std::copy(boxed.begin(), boxed.end(), recs);
+  std::copy(rest.begin(), rest.end(), recs + boxed.size());
+  *n_boxed = (int)boxed.size();
+  if (depth) *depth = dep;
   return nodes;
 }
 

@@ -81,8 +81,23 @@ std::vector<BvhNode> build_line_bvh(std::vector<QuadRec>& recs, std::vector<Cone
 // build_tri_bvh builds the hierarchy over records that all have one
 // (reordered in place into leaf order); empty when there are none.
 bool tri_box(const TriRec& r, double lo[3], double hi[3]);
+// The same for rays with |d|_inf <= dir_max from |o|_inf <= origin_max (the one above: kTriDirMax,
+// kTriOriginMax, bit for bit).
+bool tri_box(const TriRec& r, double dir_max, double origin_max, double lo[3], double hi[3]);
 std::vector<BvhNode> build_tri_bvh(std::vector<TriRec>& recs, int leaf_size, int* depth = nullptr,
                                    double trav_cost = 1.0);
+
+// The run hierarchies inside wide and deep Csg units (rt_layout.hpp CsgRun, rt_slab.hpp
+// csg_run_walk, DESIGN.md §5.2 "Csg units: run hierarchies"). csg_run_bounds: bounds on |d|_inf and
+// |o|_inf of the ray chained down `n` Csg inverses (3x4, the outermost first) from a world ray
+// within kTriDirMax / kTriOriginMax. build_csg_run: the hierarchy over the run's records
+// recs[0 .. n): each one's box is tri_box with the run's bounds, in the space of the chained ray;
+// the boxed records come first, in leaf order, the ones tri_box refuses after them (the remainder,
+// tested by every ray); `n_boxed` receives the former's count. Empty, with the records untouched:
+// fewer than `min_boxed` boxed records, or a tree deeper than kBvhMaxDepth.
+void csg_run_bounds(const double* const* chain, int n, double* dir_max, double* origin_max);
+std::vector<BvhNode> build_csg_run(TriRec* recs, int n, double dir_max, double origin_max, int min_boxed, int leaf_size,
+                                   double trav_cost, int* n_boxed, int* depth);
 
 // The Csg units' hierarchy (rt_trace.hpp unit_trace, DESIGN.md §5.2 "Csg units: the fifth
 // hierarchy"). csg_unit_box: the padded world box of one unit's program ops[first .. first + n).

@@ -11,6 +11,7 @@
 #include "rt_csg.hpp"
 #include "rt_layout.hpp"
 #include "rt_pow.hpp"
+#include "rt_slab.hpp"
 
 #pragma clang fp contract(off)
 
@@ -527,7 +528,41 @@ __device__ __forceinline__ bool csg_tri_roots(const TriRec* q, V3 o, V3 d, doubl
   return tri_local_intersect(v3(q->p1[0], q->p1[1], q->p1[2]), v3(q->e1[0], q->e1[1], q->e1[2]),
                              v3(q->e2[0], q->e2[1], q->e2[2]), lo, ld, t, u, v);
 }
-template <bool SHADOW>
+// A run's hierarchy in place of its one-by-one ops (rt_slab.hpp csg_run_walk; DESIGN.md §5.2 "Csg
+// units: run hierarchies"): at the first op of a run that has one, in a launch that walks them
+// (DevScene::csg_runs), for a chained ray the run's bounds admit. Each reached triangle does what
+// its kCsgTri op does: csg_tri_roots, then csg_batch_insert with the same key and tag. The visiting
+// order is free (csg_run_walk). True: the run is done, the caller goes on past it (op.skip_to).
+// The walk itself stays out of line: its slab constants, stack and node in flight are then a frame of its own,
+// and the scenes that walk run faster for it (csg_mesh_scene 59 -> 50 ms a frame, csg_mesh_big 18 -> 14,
+// profiles/csg_run_ab.txt). What the walk's presence costs the one-by-one ops is the same either way: the kernels
+// of scenes without a run are compiled without it (RUNS = false).
+template <typename Tag>
+__device__ __noinline__ void csg_run_walk_into(const CsgRun* rp, const BvhNode* nodes, const TriRec* tris, V3 co, V3 cd, float t_lo,
+                                               float t_hi, CsgBatchT<Tag>* b, Tag tag, double wt, int32_t wk, bool* more) {
+  const CsgRun run = *rp;
+  const TriRec* recs = tris + run.first;
+  bool m = *more;
+  csg_run_walk(run, nodes + run.node, co, cd, t_lo, t_hi, [&](int k) {
+    const TriRec* q = recs + k;
+    double t;
+    if (csg_tri_roots(q, co, cd, t)) csg_batch_insert(*b, kCsgListCap, t, (q->meta >> 1) << kKeyShift, tag, wt, wk, m);
+  });
+  *more = m;
+}
+template <typename Tag>
+__device__ __forceinline__ bool csg_run_eval(const DevScene& sc, const CsgOp op, V3 co, V3 cd, double t_stop, CsgBatchT<Tag>& b,
+                                             Tag tag, double wt, int32_t wk, bool& more) {
+  // (one op a run carries a run's index: against the ops of the runs without a hierarchy this is the cold side)
+  if (__builtin_expect(!sc.csg_runs || op.counts <= 0, 1)) return false;
+  const CsgRun* rp = sc.csg_runs + (op.counts - 1);
+  if (!csg_run_admits(*rp, co, cd)) return false;
+  csg_run_walk_into(rp, sc.csg_run_nodes, sc.csg_tris, co, cd, f32_below(wt), f32_up(t_stop), &b, tag, wt, wk, &more);
+  return true;
+}
+// RUNS = false: a kernel that never walks a run's hierarchy: the batch kernels, and the render kernels that a scene
+// without a run or an exhaustive render launches (the walk stays out of them: they keep their registers and scratch).
+template <bool SHADOW, bool RUNS = false>
 __device__ __forceinline__ void csg_wide_eval(const DevScene& sc, const CsgUnit un, V3 o, V3 d, Hit& h, unsigned& disc,
                                               GateSkips& sk) {
   CsgBatch b;
@@ -574,6 +609,12 @@ __device__ __forceinline__ void csg_wide_eval(const DevScene& sc, const CsgUnit 
           continue;
         }
       } else if (op.code == kCsgTri) {
+        if constexpr (RUNS) {
+          if (csg_run_eval(sc, op, co, cd, h.t, b, (uint16_t)(node | kCsgTagTri), wt, wk, more)) {
+            pc = op.skip_to;
+            continue;
+          }
+        }
         const TriRec* q = sc.csg_tris + op.arg;
         double t;
         if (csg_tri_roots(q, co, cd, t))
@@ -648,7 +689,7 @@ __device__ __forceinline__ void csg_deep_load(const CsgDeepWords& st, int at, V3
   o = v3(v[0], v[1], v[2]);
   d = v3(v[3], v[4], v[5]);
 }
-template <bool SHADOW, bool COUNT_ONLY>
+template <bool SHADOW, bool COUNT_ONLY, bool RUNS = false>
 __device__ __forceinline__ void csg_deep_eval(const DevScene& sc, const CsgUnit un, V3 o, V3 d, Hit& h, unsigned& disc,
                                               GateSkips& sk) {
   const unsigned lane = blockIdx.x * blockDim.x + threadIdx.x;
@@ -705,6 +746,12 @@ __device__ __forceinline__ void csg_deep_eval(const DevScene& sc, const CsgUnit 
           }
         } else if (COUNT_ONLY) {
         } else if (op.code == kCsgTri) {
+          if constexpr (RUNS) {  // (dh.t: what csg_deep_step's stop compares against; it moves only where a pass ends)
+            if (csg_run_eval(sc, op, co, cd, dh.t, b, (uint32_t)node | kCsgDeepTagTri, wt, wk, more)) {
+              pc = op.skip_to;
+              continue;
+            }
+          }
           const TriRec* q = sc.csg_tris + op.arg;
           double t;
           if (csg_tri_roots(q, co, cd, t))
@@ -758,7 +805,7 @@ __device__ __forceinline__ void csg_deep_eval(const DevScene& sc, const CsgUnit 
 // the fast path the units outside the hierarchy (trace_rest; unit_trace walks the others).
 // DEEP = false: a kernel that is launched only for scenes without a deep unit (the batch kernels have such
 // twins: the deep evaluator stays out of them, and they keep their registers).
-template <bool SHADOW, bool COUNT_ONLY, bool DEEP = true>
+template <bool SHADOW, bool COUNT_ONLY, bool DEEP = true, bool RUNS = false>
 __device__ __forceinline__ void csg_units(const DevScene& sc, const CsgUnit* units, int n, V3 o, V3 d, Hit& h,
                                           unsigned& n_disc, GateSkips* skips) {
   GateSkips sk;
@@ -772,8 +819,8 @@ __device__ __forceinline__ void csg_units(const DevScene& sc, const CsgUnit* uni
       continue;
     }
     un.n &= ~kCsgKindMask;
-    if (deep) csg_deep_eval<SHADOW, COUNT_ONLY>(sc, un, o, d, h, disc, sk);
-    else if (!COUNT_ONLY && wide) csg_wide_eval<SHADOW>(sc, un, o, d, h, disc, sk);
+    if (deep) csg_deep_eval<SHADOW, COUNT_ONLY, RUNS>(sc, un, o, d, h, disc, sk);
+    else if (!COUNT_ONLY && wide) csg_wide_eval<SHADOW, RUNS>(sc, un, o, d, h, disc, sk);
     else csg_unit_eval<SHADOW, COUNT_ONLY>(sc, un, o, d, h, disc, sk);  // (a wide unit's gates alone: the same walk)
   }
   n_disc += disc;
@@ -906,7 +953,7 @@ __device__ __forceinline__ void alias_finish(const DevScene& sc, Hit& h) {
 // units' hierarchy (fx_units; unit_trace walks the others).
 // ALIAS (with CSG): the alias classes too (alias_classes), every member on either path.
 template <bool SHADOW, bool QUADS = true, bool FAST = false, bool TRIS = QUADS, bool CSG = false, bool ALIAS = false,
-          bool DEEP = true>
+          bool DEEP = true, bool RUNS = false>
 __device__ __forceinline__ void trace_rest(const DevScene& sc, V3 o, V3 d, Hit& h, unsigned& n_disc,
                                            GateSkips* skips = nullptr) {
   cSphereGen sg = (cSphereGen)(FAST ? sc.fx_gen : sc.sph_gen);
@@ -957,7 +1004,7 @@ __device__ __forceinline__ void trace_rest(const DevScene& sc, V3 o, V3 d, Hit& 
     }
   }
   if constexpr (CSG)
-    csg_units<SHADOW, false, DEEP>(sc, FAST ? sc.fx_units : sc.csg_units, FAST ? sc.n_fx_units : sc.n_csg_units, o, d, h,
+    csg_units<SHADOW, false, DEEP, RUNS>(sc, FAST ? sc.fx_units : sc.csg_units, FAST ? sc.n_fx_units : sc.n_csg_units, o, d, h,
                                    n_disc, skips);
   if constexpr (ALIAS) alias_classes<SHADOW>(sc, o, d, h, n_disc, skips);
 }
@@ -1026,14 +1073,14 @@ __device__ __forceinline__ void diag_test(cSphereDiag r, V3 o, V3 d, Hit& h, uns
 // the wavefront fallback when the trace image does not fit in LDS.
 // TRIS = false: a scene without solids or triangles (trace_rest). CSG: one with Csg units.
 // ALIAS (with CSG): one with alias classes.
-// DEEP (with CSG): the deep units' evaluator too (csg_units).
-template <bool SHADOW, bool TRIS = true, bool CSG = false, bool ALIAS = false, bool DEEP = true>
+// DEEP (with CSG): the deep units' evaluator too (csg_units). RUNS: the run hierarchies' walk too.
+template <bool SHADOW, bool TRIS = true, bool CSG = false, bool ALIAS = false, bool DEEP = true, bool RUNS = false>
 __device__ __forceinline__ void trace(const DevScene& sc, V3 o, V3 d, Hit& h, unsigned& n_disc,
                                       GateSkips* skips = nullptr) {
   hit_init(h);
   cSphereDiag sd = (cSphereDiag)sc.sph_diag;
   for (int j = 0; j < sc.n_diag; ++j) diag_test<SHADOW>(sd + j, o, d, h, n_disc);
-  trace_rest<SHADOW, true, false, TRIS, CSG, ALIAS, DEEP>(sc, o, d, h, n_disc, skips);
+  trace_rest<SHADOW, true, false, TRIS, CSG, ALIAS, DEEP, RUNS>(sc, o, d, h, n_disc, skips);
   hit_finish(h);
   if constexpr (ALIAS && !SHADOW) alias_finish(sc, h);
 }

@@ -149,6 +149,24 @@ constexpr int32_t kCsgDeepMaxNodes = 1 << 15, kCsgDeepMaxLeaves = 1 << 16;
 struct alignas(16) CsgUnit {
   int32_t first, n, gate, counts;
 };
+// A RUN: a maximal sequence of consecutive kCsgTri ops of a wide or deep unit's program. All its
+// ops sit between the same Enter / Group gates, so the evaluators hand every one of them the same
+// chained ray. A run of at least csg_run_min boxed triangles has a hierarchy over them (DESIGN.md
+// §5.2 "Csg units: run hierarchies"; rt_slab.hpp csg_run_walk): its records are csg_tris[first ..
+// first + n), the boxed ones first and in leaf order, then the remainder (those tri_box refuses),
+// which every ray tests; its nodes csg_run_nodes[node .. node + n_nodes), child indices and leaf
+// codes (first << 7 | cnt) relative to the run. The boxes are in the space of the chained ray and
+// padded for chained rays with |d|_inf <= dmax from |o|_inf <= omax (derived from the CsgRec::m
+// chain above the run); any other chained ray takes the run's ops one by one. The run's first op
+// carries skip_to = the pc past the run and counts = 1 + the run's index (both zero in every
+// other kCsgTri op; csg_unit_eval's gates-only walk reads neither).
+struct alignas(64) CsgRun {
+  double dmax, omax;
+  int32_t first, n, n_boxed;
+  int32_t node, n_nodes, depth;
+  int64_t pad[3];
+};
+static_assert(sizeof(CsgRun) == 64, "CsgRun must stay 64 B");
 // The deep state of one lane, in 32-bit words (word i of lane l at i * lanes + l, so a wave's
 // accesses coalesce): the filter bits inl and inr, one bit each per Csg node of the unit (nw words
 // each), the parity bits of the leaves of kinds 0-4 (lw words), and per open level of the ray
@@ -453,6 +471,14 @@ struct DevScene {
   uint32_t* csg_deep_state;
   uint32_t csg_deep_lanes;
   int32_t csg_deep_nw, csg_deep_lw, csg_deep_levels;
+  // Run hierarchies (CsgRun). `csg_run_recs` / `csg_run_nodes`: the scene's runs and their nodes
+  // (nullptr without one). `csg_runs`: what a launch walks: csg_run_recs in the copy of this struct
+  // a fast-path render launches with (Wavefront::render), nullptr in the scene's own, so the
+  // exhaustive renders and the batch entry points test every triangle of a run.
+  const CsgRun* csg_runs;
+  const CsgRun* csg_run_recs;
+  const BvhNode* csg_run_nodes;
+  int32_t n_csg_runs, pad_runs;
 };
 
 constexpr int32_t kOwnOutside = 0x40000000, kOwnIndex = 0x3FFFFFFF;  // DevScene::obj_diag

@@ -483,6 +483,56 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
     if (!in_order)
       return fail(RT_ERR_INVALID_ARGUMENT, "the shapes under a Csg are not in depth-first order (left before right)");
   }
+  // ---- the run hierarchies (rt_layout.hpp CsgRun): per maximal sequence of kCsgTri ops, whose
+  // records are consecutive in csg_tris (the shapes come depth first), bounds on the chained ray
+  // from the Csg inverses above it, then a hierarchy over the boxed records when there are
+  // g_csg_run_min of them. The records are put in leaf order inside their own range, the remainder
+  // last: the ops keep their `arg`, so each names another record of the same run than before, and
+  // nothing depends on the order inside a run (the batch is ordered by (t, key), keys come from
+  // `meta`, the shading record from `tri`).
+  std::vector<CsgRun> csg_runs;
+  std::vector<BvhNode> csg_run_nodes;
+  long long run_plan[4] = {0, 0, 0, 0};  // triangles boxed, remainder, nodes, greatest depth
+  for (const CsgUnit& u : csg_units) {
+    std::vector<const double*> chain;
+    const int32_t end = u.first + (u.n & ~kCsgKindMask);
+    for (int32_t pc = u.first; pc < end;) {
+      const CsgOp& op = csg_ops[(size_t)pc];
+      if (op.code == kCsgEnter) chain.push_back(csg_nodes[(size_t)op.arg].m);
+      else if (op.code == kCsgExit && !chain.empty()) chain.pop_back();
+      if (op.code != kCsgTri) {
+        ++pc;
+        continue;
+      }
+      int32_t past = pc + 1;
+      while (past < end && csg_ops[(size_t)past].code == kCsgTri && csg_ops[(size_t)past].arg == op.arg + (past - pc)) ++past;
+      const int32_t n = past - pc;
+      if (n >= g_csg_run_min && csg_runs.size() < (size_t)INT32_MAX - 1) {
+        CsgRun run{};
+        csg_run_bounds(chain.data(), (int)chain.size(), &run.dmax, &run.omax);
+        int n_boxed = 0, depth = 0;
+        const std::vector<BvhNode> nodes = build_csg_run(&csg_tris[(size_t)op.arg], n, run.dmax, run.omax, g_csg_run_min,
+                                                         leaf, g_bvh_ct / 100.0, &n_boxed, &depth);
+        if (!nodes.empty()) {
+          run.first = op.arg;
+          run.n = n;
+          run.n_boxed = n_boxed;
+          run.node = (int32_t)csg_run_nodes.size();
+          run.n_nodes = (int32_t)nodes.size();
+          run.depth = depth;
+          csg_run_nodes.insert(csg_run_nodes.end(), nodes.begin(), nodes.end());
+          csg_runs.push_back(run);
+          csg_ops[(size_t)pc].skip_to = past;
+          csg_ops[(size_t)pc].counts = (int32_t)csg_runs.size();  // 1 + the run's index
+          run_plan[0] += n_boxed;
+          run_plan[1] += n - n_boxed;
+          run_plan[2] += (long long)nodes.size();
+          run_plan[3] = std::max<long long>(run_plan[3], depth);
+        }
+      }
+      pc = past;
+    }
+  }
   std::vector<GroupRec> grec(n_nodes);
   for (size_t g = 0; g < n_nodes; ++g) {
     for (int c = 0; c < 3; ++c) { grec[g].lo[c] = nodes[g].min[c]; grec[g].hi[c] = nodes[g].max[c]; }
@@ -633,7 +683,10 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
   const size_t o_ct = align(o_ao + (alias_of.size() + 1) * sizeof(int32_t));
   if (!deep_plan[0]) csg_counts.clear();  // (only a deep unit's gates read them)
   const size_t o_dc = align(o_ct + (csg_tris.size() + 1) * sizeof(TriRec));
-  const size_t total = align(o_dc + (csg_counts.size() + 1) * sizeof(uint32_t)) + 256;
+  // (the run hierarchies: a scene without one allocates nothing for them)
+  const size_t o_rr = align(o_dc + (csg_counts.size() + 1) * sizeof(uint32_t));
+  const size_t o_rn = csg_runs.empty() ? o_rr : align(o_rr + (csg_runs.size() + 1) * sizeof(CsgRun));
+  const size_t total = (csg_runs.empty() ? o_rr : align(o_rn + (csg_run_nodes.size() + 1) * sizeof(BvhNode))) + 256;
   std::vector<unsigned char> host(total, 0);
   if (!diag.empty()) std::memcpy(&host[o_diag], diag.data(), diag.size() * sizeof(SphereDiag));
   if (!gen.empty()) std::memcpy(&host[o_gen], gen.data(), gen.size() * sizeof(SphereGen));
@@ -688,6 +741,10 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
   if (!csg_leaves.empty()) std::memcpy(&host[o_cl], csg_leaves.data(), csg_leaves.size() * sizeof(OtherRec));
   if (!csg_tris.empty()) std::memcpy(&host[o_ct], csg_tris.data(), csg_tris.size() * sizeof(TriRec));
   if (!csg_counts.empty()) std::memcpy(&host[o_dc], csg_counts.data(), csg_counts.size() * sizeof(uint32_t));
+  if (!csg_runs.empty()) {
+    std::memcpy(&host[o_rr], csg_runs.data(), csg_runs.size() * sizeof(CsgRun));
+    std::memcpy(&host[o_rn], csg_run_nodes.data(), csg_run_nodes.size() * sizeof(BvhNode));
+  }
   if (!ubvh.empty()) std::memcpy(&host[o_ub], ubvh.data(), ubvh.size() * sizeof(BvhNode));
   if (!urec.empty()) std::memcpy(&host[o_ur], urec.data(), urec.size() * sizeof(CsgUnit));
   if (!fx_units.empty()) std::memcpy(&host[o_ux], fx_units.data(), fx_units.size() * sizeof(CsgUnit));
@@ -791,6 +848,12 @@ int create_tree(const rt_shape_desc* shapes, size_t n_shapes, const int32_t* sha
     s->dev.csg_deep_lw = (int32_t)((deep_plan[3] + 31) / 32);
   }
   for (int k = 0; k < 4; ++k) s->csg_deep_plan[k] = deep_plan[k];
+  if (!csg_runs.empty()) {  // (csg_runs itself stays null here: a fast-path render sets it in its own copy)
+    s->dev.csg_run_recs = (const CsgRun*)(b + o_rr);
+    s->dev.csg_run_nodes = (const BvhNode*)(b + o_rn);
+    s->dev.n_csg_runs = (int32_t)csg_runs.size();
+  }
+  for (int k = 0; k < 4; ++k) s->csg_run_plan[k] = run_plan[k];
   s->dev.n_csg_units = (int32_t)csg_units.size();
   s->dev.n_csg_sph = n_csg_kind[0];
   s->dev.n_csg_planes = n_csg_kind[1];

@@ -79,69 +79,7 @@ __device__ __forceinline__ bool shadow_irrelevant(const ShadeRec& m, cLightRec L
 typedef const RT_CONST BvhNode* cBvhNode;
 typedef const RT_CONST PrimRec* cPrimRec;
 
-// The per-lane traversal's slab test runs in binary32 on an interval that is
-// widened to contain the exact (real-arithmetic) one; DESIGN.md §5.2 has the
-// error bound. Per ray and axis: inv = an approximate reciprocal of d in
-// binary32 (slab_inv: relative error below 2^-22, exactly the value the FMAs
-// use), and the plane constants c = o*inv -/+ delta with delta = 2^-20 |inv|
-// (M + |o|), where M bounds every box coordinate on that axis (the root's
-// children); the computed entry (exit) distance fma(corner, inv, -c) then
-// never exceeds (falls short of) the exact one, (corner - o) / d: its error,
-// the reciprocal's included, is below delta/3.
-// An axis whose direction is (nearly) zero or whose origin is huge / NaN is
-// not used for culling at all (interval (-inf, +inf)).
-struct SlabRay {
-  float inv[3], c_lo[3], c_hi[3];
-};
-// binary32 reciprocal of a binary64 direction component with 2^-60 <= |d|:
-// (float)d rounds once (2^-24), v_rcp_f32 is within 1 ulp (2^-23); returned
-// widened to binary64 (exact), the value every plane constant is built from.
-__device__ __forceinline__ double slab_inv(double d) { return (double)__builtin_amdgcn_rcpf((float)d); }
-// `grow` (other_trace's far origins): every box taken as that much larger on each axis, in world units.
-__device__ __forceinline__ SlabRay slab_ray(V3 o, V3 d, const float* M, const double* grow = nullptr) {
-  SlabRay r;
-  const double oa[3] = {o.x, o.y, o.z}, da[3] = {d.x, d.y, d.z};
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    if (fabs(da[a]) >= 0x1p-60 && fabs(oa[a]) <= 0x1p60 && M[a] <= 0x1p60f) {  // NaN fails
-      const double inv = slab_inv(da[a]);
-      const double oinv = oa[a] * inv;
-      double delta = 0x1p-20 * fabs(inv) * ((double)M[a] + fabs(oa[a]));
-      if (grow) delta = (delta + fabs(inv) * grow[a]) * (1.0 + 0x1p-20);
-      const float on = (float)(oinv + delta), of = (float)(oinv - delta);
-      r.inv[a] = (float)inv;
-      r.c_lo[a] = inv >= 0.0 ? on : of;  // the lo plane is the entry plane when inv >= 0
-      r.c_hi[a] = inv >= 0.0 ? of : on;
-    } else {
-      r.inv[a] = 0.0f;
-      r.c_lo[a] = INFINITY;
-      r.c_hi[a] = -INFINITY;
-    }
-  }
-  return r;
-}
-// binary32 upper bound of a non-negative binary64 distance: RN(x) is within
-// 2^-23 of x relative to it, and RN(f * (1 + 2^-22)) > f * (1 + 2^-23)
-// (0 and inf map to themselves).
-__device__ __forceinline__ float f32_up(double x) { return (float)x * (1.0f + 0x1p-22f); }
-// max(entry, t_lo) <= min(exit, t_hi): the ray may meet the box within [t_lo, t_hi]
-// (t_hi >= 0). `t_in` = the widened entry distance (child ordering only).
-template <typename P>  // P: constant-address (scalar loads) or generic (per-lane loads) float pointer
-__device__ __forceinline__ bool slab_hit32(P lo, P hi, const SlabRay& r, float t_hi, float& t_in, float t_lo = 0.0f) {
-  const float x0 = fmaf(lo[0], r.inv[0], -r.c_lo[0]), x1 = fmaf(hi[0], r.inv[0], -r.c_hi[0]);
-  const float y0 = fmaf(lo[1], r.inv[1], -r.c_lo[1]), y1 = fmaf(hi[1], r.inv[1], -r.c_hi[1]);
-  const float z0 = fmaf(lo[2], r.inv[2], -r.c_lo[2]), z1 = fmaf(hi[2], r.inv[2], -r.c_hi[2]);
-  const float tmin = fmaxf(fmaxf(fminf(x0, x1), fminf(y0, y1)), fmaxf(fminf(z0, z1), t_lo));
-  const float tmax = fminf(fminf(fmaxf(x0, x1), fmaxf(y0, y1)), fminf(fmaxf(z0, z1), t_hi));
-  t_in = tmin;
-  return tmin <= tmax;
-}
-// slab_ray's M of a hierarchy: the root's two child boxes contain every box below them.
-template <typename P>  // P: constant-address or generic node pointer
-__device__ __forceinline__ void root_bound(P root, float M[3]) {
-  for (int a = 0; a < 3; ++a)
-    M[a] = fmaxf(fmaxf(fabsf(root->lo[0][a]), fabsf(root->hi[0][a])), fmaxf(fabsf(root->lo[1][a]), fabsf(root->hi[1][a])));
-}
+// The per-lane traversal's slab test (binary32, on a widened interval): rt_slab.hpp.
 
 template <bool PRIMARY, bool SHADOW>
 __device__ __forceinline__ void bvh_trace(const DevScene& sc, cPrimRec prim, int* stk, V3 o, V3 d, double t_shadow,
@@ -1233,7 +1171,8 @@ __device__ __forceinline__ void lb_walk(const DevScene& sc, SD sd, const float* 
 // TRIS: the scene has triangles (trace_rest's loop over those outside the hierarchy, tri_trace).
 // CSG: the scene has Csg units (trace_rest's csg_units over those outside their hierarchy, unit_trace).
 // ALIAS: the scene has alias classes (trace_rest's alias_classes: ordinary blockers here).
-template <bool QUADS, bool TALLY = false, bool TRIS = false, bool CSG = false, bool ALIAS = false, typename Image>
+// RUNS: the launch walks the run hierarchies inside the wide and deep units (csg_units).
+template <bool QUADS, bool TALLY = false, bool TRIS = false, bool CSG = false, bool ALIAS = false, bool RUNS = false, typename Image>
 __device__ __forceinline__ bool shadow_trace(const DevScene& sc, unsigned use_lb, const Image& img, unsigned l,
                                              V3 o, V3 d, double dist, unsigned& n_disc, unsigned& n_tests,
                                              unsigned& n_boxes, GateSkips* skips = nullptr, int first = -1,
@@ -1250,7 +1189,7 @@ __device__ __forceinline__ bool shadow_trace(const DevScene& sc, unsigned use_lb
       return true;
     }
   }
-  trace_rest<true, QUADS, true, TRIS, CSG, ALIAS>(sc, o, d, h, n_disc, skips);
+  trace_rest<true, QUADS, true, TRIS, CSG, ALIAS, true, RUNS>(sc, o, d, h, n_disc, skips);
   if constexpr (QUADS) {
     other_trace<true>(sc, o, d, dist, h, n_disc, n_tests, n_boxes);
     line_trace<true>(sc, o, d, dist, h, n_tests, n_boxes);

@@ -328,32 +328,33 @@ static hipError_t launch_timed(K kern, int block, size_t dyn, unsigned n, hipStr
 // ---- the exhaustive pipeline (counted launches: the reference's every-shape loop)
 // CSG (with QUADS): the scene has Csg units (kernels of their own, as the fused ones).
 // ALIAS (with CSG): it has alias classes (again kernels of their own).
-template <bool QUADS, bool CSG = false, bool ALIAS = false>
+// RUNS (with CSG): the launch walks the scene's run hierarchies (sc.csg_runs is set; again kernels of their own).
+template <bool QUADS, bool CSG = false, bool ALIAS = false, bool RUNS = false>
 static hipError_t launch_closest_exh(const DevScene& sc, const DevCamera& cam, const WfArgs& a, bool primary,
                                      bool lds_ok, unsigned n, hipStream_t stream, const WfTuning& tn) {
   const int tb = trace_block(n, tn.adaptive_block);
   if (primary)
-    return launch_timed(wf_trace_closest<true, true, QUADS, 8, CSG, ALIAS>, tb, wf_lds_bytes(sc.n_diag, sc.n_gen, sc.n_planes, true),
+    return launch_timed(wf_trace_closest<true, true, QUADS, 8, CSG, ALIAS, RUNS>, tb, wf_lds_bytes(sc.n_diag, sc.n_gen, sc.n_planes, true),
                         n, stream, sc, cam, a);
   if (lds_ok)
-    return launch_timed(wf_trace_closest<true, false, QUADS, 8, CSG, ALIAS>, tb,
+    return launch_timed(wf_trace_closest<true, false, QUADS, 8, CSG, ALIAS, RUNS>, tb,
                         wf_lds_bytes(sc.n_diag, sc.n_gen, sc.n_planes, false), n, stream, sc, cam, a);
-  return launch_timed(wf_trace_closest<false, false, QUADS, 8, CSG, ALIAS>, tb, 0, n, stream, sc, cam, a);
+  return launch_timed(wf_trace_closest<false, false, QUADS, 8, CSG, ALIAS, RUNS>, tb, 0, n, stream, sc, cam, a);
 }
-template <bool QUADS, bool CSG = false, bool ALIAS = false>
+template <bool QUADS, bool CSG = false, bool ALIAS = false, bool RUNS = false>
 static hipError_t launch_shadow_exh(const DevScene& sc, const WfArgs& a, bool lds_ok, hipStream_t stream,
                                     const WfTuning& tn) {
   const int tb = trace_block(a.n_shadow, tn.adaptive_block);
   if (lds_ok)
-    return launch_timed(wf_trace_shadow<true, QUADS, 8, CSG, ALIAS>, tb, wf_lds_bytes(sc.n_diag, sc.n_gen, sc.n_planes, false),
+    return launch_timed(wf_trace_shadow<true, QUADS, 8, CSG, ALIAS, RUNS>, tb, wf_lds_bytes(sc.n_diag, sc.n_gen, sc.n_planes, false),
                         a.n_shadow, stream, sc, a);
-  return launch_timed(wf_trace_shadow<false, QUADS, 8, CSG, ALIAS>, tb, 0, a.n_shadow, stream, sc, a);
+  return launch_timed(wf_trace_shadow<false, QUADS, 8, CSG, ALIAS, RUNS>, tb, 0, a.n_shadow, stream, sc, a);
 }
 
 // ---- the fast path: one fused launch per generation over the image wf_plan_image chooses
 // (rt_wf_plan.hpp); `ran` receives the plan. The global-memory images' launches live in their
 // own code object (rt_wavefront_glb.o).
-template <bool QUADS, bool TALLY, bool TRIS = false, bool CSG = false, bool ALIAS = false>
+template <bool QUADS, bool TALLY, bool TRIS = false, bool CSG = false, bool ALIAS = false, bool RUNS = false>
 static hipError_t launch_fused_q(const DevScene& sc, const DevCamera& cam, WfArgs a, bool primary, unsigned n,
                                  hipStream_t stream, const WfTuning& tn, int coresident, WfImagePlan* ran) {
   // (spread: the whole grid, whatever n; the kernel deals the chunks over every block)
@@ -370,7 +371,7 @@ static hipError_t launch_fused_q(const DevScene& sc, const DevCamera& cam, WfArg
     if (plan.coresident == 2)
       return cam_rays ? launch_timed(wf_trace_fused_cap<true>, tb, plan.dyn, n, stream, sc, cam, a)
                       : launch_timed(wf_trace_fused_cap<false>, tb, plan.dyn, n, stream, sc, cam, a);
-#define RT_LDS(P, L, C) launch_timed(wf_trace_fused<P, QUADS, L, TALLY, C, TRIS, CSG, ALIAS>, tb, plan.dyn, n, stream, sc, cam, a)
+#define RT_LDS(P, L, C) launch_timed(wf_trace_fused<P, QUADS, L, TALLY, C, TRIS, CSG, ALIAS, RUNS>, tb, plan.dyn, n, stream, sc, cam, a)
   switch (plan.lane) {
     case kLaneWave: return RT_LDS(true, kLaneWave, true);
     case kLaneWideLds: return cam_rays ? RT_LDS(false, kLaneWideLds, true) : RT_LDS(false, kLaneWideLds, false);
@@ -378,12 +379,19 @@ static hipError_t launch_fused_q(const DevScene& sc, const DevCamera& cam, WfArg
   }
 #undef RT_LDS
   if (t_ev_start) ++t_ev_used;
-  return wf_launch_global(plan.lane, QUADS, TRIS, CSG, ALIAS, TALLY, cam_rays, sc, cam, a, plan.dyn, n, stream, tb, t_ev_start, t_ev_stop);
+  return wf_launch_global(plan.lane, QUADS, TRIS, CSG, ALIAS, RUNS, TALLY, cam_rays, sc, cam, a, plan.dyn, n, stream, tb, t_ev_start, t_ev_stop);
 }
 static hipError_t launch_fused(const DevScene& sc, const DevCamera& cam, const WfArgs& a, bool primary, unsigned n,
                                hipStream_t stream, bool tally, const WfTuning& tn, int coresident, WfImagePlan* ran) {
   // QUADS: solids outside the hierarchies, or the hierarchy over the other records
   const bool quads = sc.n_fx_quads > 0 || sc.n_obvh > 0 || sc.n_lbvh > 0;
+  if (sc.csg_runs) {  // (the Csg and alias kernels that walk the run hierarchies: a scene that has one, not exhaustive)
+    if (sc.n_alias_rec > 0)
+      return tally ? launch_fused_q<true, true, true, true, true, true>(sc, cam, a, primary, n, stream, tn, coresident, ran)
+                   : launch_fused_q<true, false, true, true, true, true>(sc, cam, a, primary, n, stream, tn, coresident, ran);
+    return tally ? launch_fused_q<true, true, true, true, false, true>(sc, cam, a, primary, n, stream, tn, coresident, ran)
+                 : launch_fused_q<true, false, true, true, false, true>(sc, cam, a, primary, n, stream, tn, coresident, ran);
+  }
   if (sc.n_alias_rec > 0)  // (the Csg kernels with the alias classes)
     return tally ? launch_fused_q<true, true, true, true, true>(sc, cam, a, primary, n, stream, tn, coresident, ran)
                  : launch_fused_q<true, false, true, true, true>(sc, cam, a, primary, n, stream, tn, coresident, ran);
@@ -469,6 +477,10 @@ hipError_t Wavefront::render(const DevScene& scene, const WfJob& job, hipStream_
   const bool bvh = tn.accel != 0 && !exhaustive && (sc.n_bvh > 0 || sc.n_obvh > 0 || sc.n_lbvh > 0 || sc.n_tbvh > 0 ||
                                                       sc.n_ubvh > 0);
   const bool fused = bvh;
+  // the run hierarchies inside the wide and deep Csg units: every render but the exhaustive one,
+  // whichever pipeline runs it (this launch's own copy of the record: the scene's holds null)
+  sc.csg_runs = tn.accel != 0 && !exhaustive ? sc.csg_run_recs : nullptr;
+  runs_walked_ = sc.csg_runs != nullptr;
   WF_CHECK(with_deep_state(fused ? 1 : 2, &sc));
   // (a counted render of a scene with groups traces every shadow ray: the reference's shape
   // tests then come from the group gates each ray met, GateSkips)
@@ -746,7 +758,9 @@ hipError_t Wavefront::render_exhaustive(const DevScene& sc, const WfJob& job, hi
     a.disc_slot = (unsigned)ccls;
     prof_rays_[ccls] += n;
     WF_CHECK(pmark(stream, ccls, true));
-    if (sc.n_alias_rec > 0) WF_CHECK((launch_closest_exh<true, true, true>(sc, cam, a, prim_launch, gen_lds, n, stream, tn)));
+    if (sc.n_alias_rec > 0 && sc.csg_runs) WF_CHECK((launch_closest_exh<true, true, true, true>(sc, cam, a, prim_launch, gen_lds, n, stream, tn)));
+    else if (sc.n_alias_rec > 0) WF_CHECK((launch_closest_exh<true, true, true>(sc, cam, a, prim_launch, gen_lds, n, stream, tn)));
+    else if (sc.csg_runs) WF_CHECK((launch_closest_exh<true, true, false, true>(sc, cam, a, prim_launch, gen_lds, n, stream, tn)));
     else if (sc.n_csg_units > 0) WF_CHECK((launch_closest_exh<true, true>(sc, cam, a, prim_launch, gen_lds, n, stream, tn)));
     else if (sc.n_quads > 0 || sc.n_tris > 0) WF_CHECK(launch_closest_exh<true>(sc, cam, a, prim_launch, gen_lds, n, stream, tn));
     else WF_CHECK(launch_closest_exh<false>(sc, cam, a, prim_launch, gen_lds, n, stream, tn));
@@ -786,7 +800,9 @@ hipError_t Wavefront::render_exhaustive(const DevScene& sc, const WfJob& job, hi
       WF_CHECK(pmark(sh_stream, WF_SHADOW, true));
       // (beside the next generation's closest-hit launch on the side stream: the deep Csg units' second state set)
       const DevScene sc_sh = sh_stream != stream ? deep_side_scene(sc) : sc;
-      if (sc.n_alias_rec > 0) WF_CHECK((launch_shadow_exh<true, true, true>(sc_sh, a, gen_lds, sh_stream, tn)));
+      if (sc.n_alias_rec > 0 && sc.csg_runs) WF_CHECK((launch_shadow_exh<true, true, true, true>(sc_sh, a, gen_lds, sh_stream, tn)));
+      else if (sc.n_alias_rec > 0) WF_CHECK((launch_shadow_exh<true, true, true>(sc_sh, a, gen_lds, sh_stream, tn)));
+      else if (sc.csg_runs) WF_CHECK((launch_shadow_exh<true, true, false, true>(sc_sh, a, gen_lds, sh_stream, tn)));
       else if (sc.n_csg_units > 0) WF_CHECK((launch_shadow_exh<true, true>(sc_sh, a, gen_lds, sh_stream, tn)));
       else if (sc.n_quads > 0 || sc.n_tris > 0) WF_CHECK(launch_shadow_exh<true>(sc, a, gen_lds, sh_stream, tn));
       else WF_CHECK(launch_shadow_exh<false>(sc, a, gen_lds, sh_stream, tn));

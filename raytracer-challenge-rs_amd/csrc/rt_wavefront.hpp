@@ -147,7 +147,7 @@ struct WfImagePlan {
 // built without the scheduler's trackers). e0/e1: launch-carried profiling
 // events, or null.
 struct WfArgs;
-hipError_t wf_launch_global(int lane, bool quads, bool tris, bool csg, bool alias, bool tally, bool cam_rays, const DevScene& sc, const DevCamera& cam,
+hipError_t wf_launch_global(int lane, bool quads, bool tris, bool csg, bool alias, bool runs, bool tally, bool cam_rays, const DevScene& sc, const DevCamera& cam,
                             const WfArgs& a, size_t dyn, unsigned n, hipStream_t stream, int block, hipEvent_t e0,
                             hipEvent_t e1);
 
@@ -458,6 +458,8 @@ class Wavefront {
   // The bytes of deep-Csg state the last render asked for and could not allocate (it returned
   // hipErrorOutOfMemory), else 0.
   size_t deep_asked() const { return deep_asked_; }
+  // The last render walked the scene's run hierarchies (DevScene::csg_runs was set in its launches' scene).
+  bool runs_walked() const { return runs_walked_; }
 
  private:
   // The scene as this workspace's launches see it: with this workspace's state buffer for the
@@ -522,6 +524,7 @@ class Wavefront {
   // the last render's fused launches: generation 0's image, the last deeper generation's (lane -1: none)
   WfImagePlan plan_primary_, plan_secondary_;
   bool gen_ev_done_ = false;  // gen_event_recorded()
+  bool runs_walked_ = false;
   bool profiling_ = false;
   int pmask_ = (1 << WF_NCLASS) - 1;
   std::vector<hipEvent_t> pev_;        // event pool (pairs)

@@ -310,7 +310,7 @@ __device__ WfLds wf_lds_stage(const DevScene& sc, const PrimRec* prim, unsigned 
 // or the shadow-caster variant). Sphere records are read as wave-uniform
 // ds_read_b128 broadcasts with a one-record look-ahead; the image holds zero
 // padding records, so record j+1 always exists.
-template <bool PRIMARY, bool SHADOW, bool QUADS, bool CSG = false, bool ALIAS = false>
+template <bool PRIMARY, bool SHADOW, bool QUADS, bool CSG = false, bool ALIAS = false, bool RUNS = false>
 __device__ __forceinline__ void wf_trace_lds(const DevScene& sc, const WfLds& lv, V3 o, V3 d, Hit& h,
                                              unsigned& n_disc, GateSkips& sk) {
   hit_init(h);
@@ -383,7 +383,7 @@ __device__ __forceinline__ void wf_trace_lds(const DevScene& sc, const WfLds& lv
       tri_test<SHADOW>(tr + j, o, d, h);
     }
   }
-  if constexpr (CSG) csg_units<SHADOW, false>(sc, sc.csg_units, sc.n_csg_units, o, d, h, n_disc, &sk);
+  if constexpr (CSG) csg_units<SHADOW, false, true, RUNS>(sc, sc.csg_units, sc.n_csg_units, o, d, h, n_disc, &sk);
   if constexpr (ALIAS) alias_classes<SHADOW>(sc, o, d, h, n_disc, &sk);
   hit_finish(h);
   if constexpr (ALIAS && !SHADOW) alias_finish(sc, h);
@@ -402,7 +402,9 @@ __device__ __forceinline__ void add_gate_skips(WfCounters* cnt, const GateSkips&
 }
 
 // ---------------------------------------------------------- trace kernels
-template <bool USE_LDS, bool PRIMARY, bool QUADS, int TW, bool CSG = false, bool ALIAS = false>
+// RUNS (with CSG): the launch walks the scene's run hierarchies (DevScene::csg_runs is set: a scene that has one, in a
+// render that is not exhaustive); kernels of their own, so that every other launch keeps the code it had.
+template <bool USE_LDS, bool PRIMARY, bool QUADS, int TW, bool CSG = false, bool ALIAS = false, bool RUNS = false>
 __global__ __launch_bounds__(kTraceBlock, TW) void wf_trace_closest(DevScene sc, DevCamera cam, WfArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   unsigned n_disc = 0;
@@ -417,8 +419,8 @@ __global__ __launch_bounds__(kTraceBlock, TW) void wf_trace_closest(DevScene sc,
     V3 o, d;
     wf_ray(a, cam, slot, o, d);
     Hit h;
-    if constexpr (USE_LDS) wf_trace_lds<PRIMARY, false, QUADS, CSG, ALIAS>(sc, lv, o, d, h, n_disc, sk);
-    else trace<false, QUADS, CSG, ALIAS>(sc, o, d, h, n_disc, &sk);
+    if constexpr (USE_LDS) wf_trace_lds<PRIMARY, false, QUADS, CSG, ALIAS, RUNS>(sc, lv, o, d, h, n_disc, sk);
+    else trace<false, QUADS, CSG, ALIAS, true, RUNS>(sc, o, d, h, n_disc, &sk);
     WfHit w;
     w.t = h.t; w.key = h.key; w.c1k = h.c1k; w.c2k = h.c2k; w.hin = h.hin;
     a.hits[slot] = w;
@@ -432,7 +434,7 @@ __global__ __launch_bounds__(kTraceBlock, TW) void wf_trace_closest(DevScene sc,
 // object has a root t with 0 <= t < distance (the first t >= 0 among shadow
 // casters in the sorted list is the minimum one). Full traversal: the exact
 // counters (sphere_disc_ge0) need every test.
-template <bool USE_LDS, bool QUADS, int TW, bool CSG = false, bool ALIAS = false>
+template <bool USE_LDS, bool QUADS, int TW, bool CSG = false, bool ALIAS = false, bool RUNS = false>
 __global__ __launch_bounds__(kTraceBlock, TW) void wf_trace_shadow(DevScene sc, WfArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
   unsigned n_disc = 0;
@@ -448,8 +450,8 @@ __global__ __launch_bounds__(kTraceBlock, TW) void wf_trace_shadow(DevScene sc, 
     unsigned slot;
     shadow_ray(sc, a, shard_slot<false>(pre, a.sh_cap, i), o, d, dist, slot);
     Hit h;
-    if constexpr (USE_LDS) wf_trace_lds<false, true, QUADS, CSG, ALIAS>(sc, lv, o, d, h, n_disc, sk);
-    else trace<true, QUADS, CSG, ALIAS>(sc, o, d, h, n_disc, &sk);
+    if constexpr (USE_LDS) wf_trace_lds<false, true, QUADS, CSG, ALIAS, RUNS>(sc, lv, o, d, h, n_disc, sk);
+    else trace<true, QUADS, CSG, ALIAS, true, RUNS>(sc, o, d, h, n_disc, &sk);
     shadow_result(sc, a, slot, h.key >= 0 && h.t < dist, o, d);
   }
   const unsigned long long s = wave_sum(n_disc);
@@ -671,7 +673,7 @@ struct FusedTally {
 // calls it (shard_append), `valid` false for the padding lanes. TALLY: the
 // kernel's (a counted launch; shadow_trace then counts every group gate).
 // TRIS, CSG, ALIAS: the kernel's (a scene with triangles, with Csg units, with alias classes).
-template <bool QUADS, bool CAM, bool TALLY, bool TRIS, bool CSG, bool ALIAS, typename Image>
+template <bool QUADS, bool CAM, bool TALLY, bool TRIS, bool CSG, bool ALIAS, bool RUNS, typename Image>
 __device__ __forceinline__ void shade_fused(const DevScene& sc, const DevCamera& cam, const WfArgs& a,
                                             const Image& img, unsigned q, unsigned slot, bool valid, V3 o, V3 d,
                                             const Hit& h, FusedTally& t) {
@@ -740,7 +742,7 @@ __device__ __forceinline__ void shade_fused(const DevScene& sc, const DevCamera&
     if (a.skip_shadow && shadow_irrelevant(*m, Lr, sdir, c.normal, term)) {
       // the light is behind the surface: lighting() is the ambient term either way
     } else {
-      const bool shadowed = shadow_trace<QUADS, TALLY, TRIS, CSG, ALIAS>(
+      const bool shadowed = shadow_trace<QUADS, TALLY, TRIS, CSG, ALIAS, RUNS>(
           sc, a.use_lb, img, l, c.over, sdir, dist, t.sh_disc, t.sh_tests, t.sh_boxes, &t.gsk, own_first,
           own_out >= 0 && vdot(sdir, c.normal) >= 0.0 ? own_out : -1);
       if (QUADS && a.count) count_hier_gates<TRIS, CSG>(sc, c.over, sdir, t.gsk);
@@ -787,8 +789,9 @@ __device__ __forceinline__ void shade_fused(const DevScene& sc, const DevCamera&
 // below include: a register bound is an attribute of a kernel, not of an instantiation, and a
 // function called by both changed the scratch of 32 other instantiations
 // (profiles/coresident_resources.txt), where the include leaves every one as it was.
+// RUNS (with CSG): the launch walks the scene's run hierarchies (as the trace kernels' flag above).
 template <bool PRIMARY, bool QUADS, int LANE, bool TALLY, bool CAM = PRIMARY, bool TRIS = false, bool CSG = false,
-          bool ALIAS = false>
+          bool ALIAS = false, bool RUNS = false>
 __global__ __launch_bounds__(kTraceBlock, 4) void wf_trace_fused(DevScene sc, DevCamera cam, WfArgs a) {
 #include "rt_wf_fused_body.inc"
 }
@@ -798,7 +801,7 @@ __global__ __launch_bounds__(kTraceBlock, 4) void wf_trace_fused(DevScene sc, De
 // (the attribute counts registers of one of the unified file's two halves: 60 bounds the wave's 120)
 // (the other arguments are fixed; template parameters so that the body's `if constexpr` discard as they do above)
 template <bool CAM, int LANE = kLaneWideLds, bool PRIMARY = false, bool QUADS = false, bool TALLY = false,
-          bool TRIS = false, bool CSG = false, bool ALIAS = false>
+          bool TRIS = false, bool CSG = false, bool ALIAS = false, bool RUNS = false>
 __global__ __launch_bounds__(kTraceBlock, 4) __attribute__((amdgpu_num_vgpr(60))) void wf_trace_fused_cap(DevScene sc,
                                                                                                            DevCamera cam,
                                                                                                            WfArgs a) {

@@ -67,7 +67,7 @@
                                       t.tests, t.boxes);
       }
       // (a per-lane walk: planes and the other records first, an early nearest hit tightens the culling)
-      trace_rest<false, QUADS, true, TRIS, CSG, ALIAS>(sc, o, d, h, t.disc, &t.gsk);
+      trace_rest<false, QUADS, true, TRIS, CSG, ALIAS, true, RUNS>(sc, o, d, h, t.disc, &t.gsk);
       if constexpr (QUADS) {
         other_trace<false>(sc, o, d, 0.0, h, t.disc, t.tests, t.boxes);
         line_trace<false>(sc, o, d, 0.0, h, t.tests, t.boxes);
@@ -89,7 +89,7 @@
     V3 o = v3(0, 0, 0), d = v3(0, 0, 0);
     Hit h;
     traverse(i, valid, slot, o, d, h);
-    shade_fused<QUADS, CAM, TALLY, TRIS, CSG, ALIAS>(sc, cam, a, img, c, slot, valid, o, d, h, t);
+    shade_fused<QUADS, CAM, TALLY, TRIS, CSG, ALIAS, RUNS>(sc, cam, a, img, c, slot, valid, o, d, h, t);
     c = dyn ? c_base + X * (unsigned)__shfl((int)k_next, 0, 64) : c + W;
   }
   if constexpr (!TALLY) return;

@@ -928,6 +928,29 @@ def csg_mesh_scene(width=640, height=360, nu=48, nv=32, divide=8, seed=0x5EED0C5
     return w, _camera(width, height, PI / 3.0, (0.0, 2.8, -6.5), (0.0, 0.8, 0.0)), depth
 
 
+def csg_mesh_big(width=640, height=360, nu=128, nv=64, seed=0x5EED0C5B, depth=5):
+    """One undivided mesh_torus(nu, nv) minus a cube on a reflective floor: a single run of 2 nu nv triangle
+    leaves in one wide unit (an OBJ file as loaded), the case the run hierarchies exist for."""
+    w = rt.World()
+    floor = rt.Plane()
+    floor.material.color = rt.Color(0.8, 0.8, 0.85)
+    floor.material.reflective = 0.25
+    floor.material.specular = 0.0
+    w.add_object(floor)
+    m = rt.Material()
+    m.color = rt.Color(0.9, 0.45, 0.2)
+    m.reflective = 0.15
+    a = _mesh_group(mesh_torus(nu, nv, False, seed), m)
+    a.set_transform(rt.translation(0.0, 1.0, 0.5) * rt.rotation_x(0.5) * rt.scaling(1.6, 1.6, 1.6))
+    cut = rt.Cube()
+    cut.set_transform(rt.translation(0.9, 1.5, -0.3) * rt.rotation_y(0.4) * rt.scaling(0.9, 0.9, 0.9))
+    cut.material.color = rt.Color(0.3, 0.3, 0.8)
+    w.add_object(rt.Csg(rt.Operation.Difference, a, cut))
+    w.add_light(rt.PointLight(rt.Point(-6.0, 8.0, -8.0), rt.Color(0.9, 0.9, 0.9)))
+    w.add_light(rt.PointLight(rt.Point(5.0, 6.0, -3.0), rt.Color(0.35, 0.35, 0.4)))
+    return w, _camera(width, height, PI / 3.0, (0.0, 2.8, -6.5), (0.0, 0.8, 0.0)), depth
+
+
 def csg_mesh_random(seed, width=24, height=16):
     """A seeded random scene of meshes under Csgs: a floor, two plain glass spheres, and two or three Csg
     trees of random operations (up to 4 levels) over tetrahedra and mesh_torus(4, 3), flat and smooth, and
